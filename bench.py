@@ -11,10 +11,12 @@ operand is split hi+lo into two bf16 values and a product is hi*hi + hi*lo + lo*
 accumulation (~2^-17 relative error per product; tests/test_gpu_model.py holds it to the same 1e-4 bar as --math f32,
 the exact-fp32-MFMA mode, whose number is reported alongside on 1 GPU).  The slice batch x is resident in HBM before the
 timed region; eps and the three dropout masks are drawn FRESH every timed step on the device (counter-based generator, one launch, inside
-the timed region).  Also reported: `trainer_loop_slices_per_s` = one process() epoch of trainers.VAE (the reference's unit of work), the
-roofline of the dominant kernel against BOTH bounds (mfma_fraction, hbm_fraction), the CPU baseline (torch-CPU oneDNN port, all physical
-cores).  N>1: slice-batch data parallel, weak scaling (64 slices per GPU), the three
-gradient segments are all-reduced over RCCL as soon as each is complete, overlapped with the rest of the backward.
+the timed region).  A plain run sets up, warms up, times exactly --steps steps and prints the headline line (value, ms_per_step).  With --full
+it also reports: `trainer_loop_slices_per_s` = one process() epoch of trainers.VAE (the reference's unit of work), the
+roofline of the dominant kernel against BOTH bounds (mfma_fraction, hbm_fraction), the other math modes, the CPU baseline (torch-CPU oneDNN port,
+all physical cores), and times --rounds 5 regions by default (the median is reported).  N>1: slice-batch data parallel, weak scaling (64 slices
+per GPU), the three gradient segments are all-reduced over RCCL as soon as each is complete, overlapped with the rest of the backward (--full adds
+the exposed-communication leg).  --dump-outputs DIR writes what the last timed step returned (and the parameters it left) as DIR/<name>.npy.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -61,6 +63,33 @@ def emit_json(obj):
     else:
         sys.stdout.flush()
         os.write(_REAL_STDOUT, line)
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: every array of `arrays` (torch tensors, numpy arrays or numbers) as directory/<name>.npy in float32 (float64 stays float64).
+    When the whole set exceeds max_bytes, each array is cut to its even share by a fixed, seeded sample of its flattened elements (sorted indices,
+    the same from run to run), so that two builds can be compared output for output."""
+    out = {}
+    for name, v in arrays.items():
+        if hasattr(v, 'detach'):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v)
+        out[name.replace('/', '_')] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > max_bytes:
+        share = max_bytes // len(out)
+        for k, (name, a) in enumerate(sorted(out.items())):
+            keep = share // a.itemsize
+            if a.size > keep:
+                idx = np.sort(np.random.default_rng(1234 + k).choice(a.size, keep, replace=False))
+                out[name] = a.reshape(-1)[idx]
+    os.makedirs(directory, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+    return sorted(out)
 
 
 def conv_layers():
@@ -347,6 +376,8 @@ def bench_gmvae(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(xr).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'x_restored': xr})
     eng.profile(True)
     xr = x0.clone()
     for _ in range(5):
@@ -489,6 +520,8 @@ def bench_gmvae_volume(args):
         t = torch.tensor([dt], device='cuda', dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in ev.items() if isinstance(v, (int, float, np.number, np.ndarray)) and not isinstance(v, bool)})
     # phase shares (untimed pass, own patient): restoration | residual + erosion + median | scoring (sort, scans, Dice sweep, small-component filter)
     ph = {}
     k = rank
@@ -720,6 +753,8 @@ def bench_fanogan(args):
 
     dt, out = timed(wgan_step, args.steps, args.warmup)
     assert bool(torch.isfinite(out['disc_loss']))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if v is not None})
     dt_e, out_e = timed(enc_step, args.steps, max(args.warmup, 1))
     assert bool(torch.isfinite(out_e['enc_loss']))
     ar_rehearsal = None
@@ -862,7 +897,13 @@ def main():
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--rounds', type=int, default=5, help='timed regions of --steps steps each; the MEDIAN round is reported (ms_per_step, value)')
+    ap.add_argument('--rounds', type=int, default=None,
+                    help='timed regions of --steps steps each; the MEDIAN round is reported (ms_per_step, value).  Default 1 (5 with --full)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: per-kernel timings and roofline, the other math modes, the trainer-loop leg, the CPU baseline, '
+                         'the exposed-communication leg (N > 1), 5 timed rounds by default')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)')
     ap.add_argument('--quick', action='store_true', help='A/B runs: skip the CPU baseline, the other math mode and the trainer-loop leg')
     ap.add_argument('--math', default=os.environ.get('UAD_BENCH_MATH', 'bf16x3'), choices=['f32', 'bf16x3', 'bf16x6', 'bf16x3_all'],
                     help='bf16x3 (default): split-bf16 products on the bf16 matrix cores, fp32 accumulate, parity 1e-4 vs the '
@@ -878,6 +919,8 @@ def main():
                     help='fAnoGAN graph: resnet = models/fanogan_schlegl.py (the one BASELINE.json configs[3] names), unified = models/fanogan.py')
     ap.add_argument('--batch', type=int, default=0, help='slices per GPU (default 64 for VAE, 16 for ceVAE)')
     args = ap.parse_args()
+    if args.rounds is None:
+        args.rounds = 5 if args.full else 1
     claim_stdout()
     global BATCH
     BATCH = args.batch or (64 if args.arch in ('VAE', 'fAnoGAN') else 16)
@@ -984,7 +1027,7 @@ def main():
         dt = float(np.median(per_round))
         loss = float(out['scalars'][2].item())
         assert np.isfinite(loss) or os.environ.get('UAD_BENCH_ALLOW_NAN'), 'loss diverged'
-        return dt, loss, [round(t / steps * 1e3, 4) for t in per_round]
+        return dt, loss, [round(t / steps * 1e3, 4) for t in per_round], out
 
     def profiled(math):
         """Roofline leg: per-launch-group HIP-event timing of the same step (profiling pass after the timed region)."""
@@ -1086,17 +1129,23 @@ def main():
                               'peak x clock / 2.4 GHz is the matrix-pipe ceiling at that clock')
         return roof
 
-    dt, loss, round_ms = timed(args.steps, args.warmup, args.rounds)
-    roof, kernels = profiled(args.math)
-    roof = with_clock(roof)
+    dt, loss, round_ms, last_out = timed(args.steps, args.warmup, args.rounds)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from the last timed step, and the parameters its Adam update left on the device
+        dump_outputs(args.dump_outputs, dict(last_out, params=eng.get_buffer_host(_lib.BUF_PARAMS)))
+    del last_out
+    roof = kernels = None
+    if args.full:
+        roof, kernels = profiled(args.math)
+        roof = with_clock(roof)
     # the other math mode, same handle, for the record (rank 0 / single GPU only; not the headline value)
     other = None
     others = []
-    if world == 1 and not args.quick:
+    if args.full and world == 1 and not args.quick:
         # exact fp32 (north_star's "fp32 MFMA roofline" mode) and bf16x6 (round 6: the fp32-GRADE mode on the bf16 matrix cores, 1e-5 parity) ride beside the default
         for om in [mm for mm in ('f32', 'bf16x6', 'bf16x3') if mm != args.math]:
             eng.set_math(om)
-            odt, _, oround_ms = timed(args.steps, max(2, args.warmup), args.rounds)
+            odt, _, oround_ms, _ = timed(args.steps, max(2, args.warmup), args.rounds)
             oroof, _ = profiled(om)
             oroof = with_clock(oroof)
             ovalue = BATCH * args.steps / odt
@@ -1110,10 +1159,10 @@ def main():
 
     # per-segment gradient all-reduce, timed on its own after the timed region (N > 1): what the backward has to hide
     allreduce = None
-    if multi:
+    if multi and args.full:
         # communication the backward did NOT hide = (step with the gradient all-reduces) - (same step without them), same ranks, same run
         dp.no_allreduce = True
-        ndt, _, nround_ms = timed(args.steps, 2, args.rounds)
+        ndt, _, nround_ms, _ = timed(args.steps, 2, args.rounds)
         dp.no_allreduce = False
         exposed_ms = (dt - ndt) / args.steps * 1e3
         names = {_lib.SEG_DECODER: 'decoder', _lib.SEG_BOTTLENECK: 'bottleneck', _lib.SEG_ENCODER_HI: 'encoder_deep', _lib.SEG_ENCODER_LO: 'encoder_first_blocks'}
@@ -1141,7 +1190,7 @@ def main():
     # the reference's unit of work is the process() loop (trainers/VAE.py:76-103): one TRAIN epoch of trainers.VAE on an HBM-resident
     # slice set -- batch gather, noise and scalar bookkeeping included -- next to the bare step above
     loop = None
-    if world == 1 and not cevae and args.arch == 'VAE' and not args.quick:
+    if args.full and world == 1 and not cevae and args.arch == 'VAE' and not args.quick:
         from unsupervised_anomaly_detection_brain_mri_amd.models import variational_autoencoder
         from unsupervised_anomaly_detection_brain_mri_amd.trainers import VAE, Phase
         from unsupervised_anomaly_detection_brain_mri_amd.utils.default_config_setup import get_config, get_options
@@ -1191,17 +1240,18 @@ def main():
                        'parallelism': f'dp{world}' if world > 1 else 'single',
                        'step_tflops': round(value * train_flops_per_slice() * (2 if cevae else 1) / 1e12, 2),
                        'final_loss': round(loss, 4)},
-            'kernels': kernels,
         }
-        res['roofline'] = roof
-        step_bytes = sum(bytes_per_tag(BATCH * (2 if cevae else 1), fin_bits=(args.math != 'f32')).values())
-        res['roofline']['whole_step'] = {
-            'algorithmic_tflops': res['config']['step_tflops'], 'mfma_fraction': round(res['config']['step_tflops'] / roof['peak'], 4),
-            'algorithmic_gbytes': round(step_bytes / 1e9, 3),
-            'hbm_fraction': round(step_bytes / (dt / args.steps) / 1e9 / PEAK_HBM_GBS, 4),
-            'mfma_fraction_at_measured_clock': (round(res['config']['step_tflops'] / roof['peak'] * SPEC_CLOCK_GHZ / roof['clock_ghz_measured'], 4)
-                                                if roof.get('clock_ghz_measured') else None),
-            'note': 'conv launch groups only (the first / final single-channel kernels, the bottleneck and Adam add < 8 % of the bytes)'}
+        if roof is not None:
+            res['kernels'] = kernels
+            res['roofline'] = roof
+            step_bytes = sum(bytes_per_tag(BATCH * (2 if cevae else 1), fin_bits=(args.math != 'f32')).values())
+            res['roofline']['whole_step'] = {
+                'algorithmic_tflops': res['config']['step_tflops'], 'mfma_fraction': round(res['config']['step_tflops'] / roof['peak'], 4),
+                'algorithmic_gbytes': round(step_bytes / 1e9, 3),
+                'hbm_fraction': round(step_bytes / (dt / args.steps) / 1e9 / PEAK_HBM_GBS, 4),
+                'mfma_fraction_at_measured_clock': (round(res['config']['step_tflops'] / roof['peak'] * SPEC_CLOCK_GHZ / roof['clock_ghz_measured'], 4)
+                                                    if roof.get('clock_ghz_measured') else None),
+                'note': 'conv launch groups only (the first / final single-channel kernels, the bottleneck and Adam add < 8 % of the bytes)'}
         if other:
             res['other_math_mode'] = other                       # exact fp32 (kept under the key earlier rounds used)
             res['other_math_modes'] = others                     # + bf16x6: fp32-grade numerics (1e-5 parity, tests/test_gpu_scale_parity.py) on the bf16 matrix cores
@@ -1210,7 +1260,7 @@ def main():
             res['trainer_loop'] = loop
         if allreduce:
             res['allreduce'] = allreduce
-        if world == 1 and not args.no_cpu_baseline and not args.quick and not cevae:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.quick and not cevae:
             res['cpu_baseline'] = cpu_baseline()
         emit_json(res)
     if multi:

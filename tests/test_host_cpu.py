@@ -369,6 +369,27 @@ def test_bench_evidence_loader_and_stdout_claim(tmp_path):
     assert 'banner' in r.stderr and 'chatter' in r.stderr
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one float32 .npy per array (float64 kept), names without '/', and above the byte cap a fixed,
+    seeded sample per array that is the same from run to run."""
+    import torch
+    import bench
+    rng = np.random.default_rng(0)
+    arrays = {'x_hat': torch.from_numpy(rng.standard_normal((4, 8, 8, 1)).astype(np.float32)), 'scalars': np.arange(8, dtype=np.float64),
+              'a/b': np.arange(5, dtype=np.int32), 'loss': 1.5}
+    names = bench.dump_outputs(str(tmp_path / 'full'), arrays)
+    assert names == ['a_b', 'loss', 'scalars', 'x_hat']
+    got = {n: np.load(tmp_path / 'full' / (n + '.npy')) for n in names}
+    assert got['x_hat'].dtype == np.float32 and np.array_equal(got['x_hat'], arrays['x_hat'].numpy())
+    assert got['scalars'].dtype == np.float64 and got['a_b'].dtype == np.float32 and float(got['loss']) == 1.5
+    big = {'p': np.arange(10000, dtype=np.float32), 'q': np.ones(10, np.float32)}
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), big, max_bytes=4000)
+    p1, p2 = np.load(tmp_path / 's1' / 'p.npy'), np.load(tmp_path / 's2' / 'p.npy')
+    assert p1.nbytes <= 2000 and np.array_equal(p1, p2) and np.all(np.diff(p1) > 0)
+    assert np.array_equal(np.load(tmp_path / 's1' / 'q.npy'), big['q'])
+
+
 def test_data_parallel_step_prefers_the_library_path_only_under_rccl(monkeypatch):
     """parallel._library_allreduce_default: the library-issued all-reduce is the default only when the process group's backend is RCCL ("nccl") and
     UAD_DP_LIBRARY_AR is not 0; gloo (every CPU test) and an uninitialised group keep the torch.distributed path."""

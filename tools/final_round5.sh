@@ -12,10 +12,10 @@ Q="--quick --no-cpu-baseline"
 cd /tmp
 prof3() {   # prof3 <tag> <bench args...>: stats + FETCH_SIZE + WRITE_SIZE passes of one bench command
   tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$tag -- python $REPO/bench.py "$@" > $OUT/${tag}_bench_under_profiler.json 2>$OUT/stats_$tag.err || true
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$tag -- python $REPO/bench.py --full "$@" > $OUT/${tag}_bench_under_profiler.json 2>$OUT/stats_$tag.err || true
   find $OUT/stats_$tag -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${tag}_kernel_stats.csv
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$tag -- python $REPO/bench.py "$@" > /dev/null 2>$OUT/fetch_$tag.err || true
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write_$tag -- python $REPO/bench.py "$@" > /dev/null 2>$OUT/write_$tag.err || true
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$tag -- python $REPO/bench.py --full "$@" > /dev/null 2>$OUT/fetch_$tag.err || true
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write_$tag -- python $REPO/bench.py --full "$@" > /dev/null 2>$OUT/write_$tag.err || true
 }
 # ---- default workload, both math modes
 prof3 vae_bf16x3 --steps 10 --warmup 3 $Q
@@ -33,8 +33,8 @@ prof3 gmvae_restore --arch GMVAE_spatial --steps 1 --warmup 1 --restore-steps 20
 python $REPO/tools/evidence.py $OUT/fetch_gmvae_restore $OUT/write_gmvae_restore $OUT/gmvae_restore_kernel_stats.csv $OUT/evidence_gmvae_restore_b16.json $COMMIT "bench.py --arch GMVAE_spatial --steps 1 --warmup 1 --restore-steps 20 --quick" > $OUT/evidence_gmvae_restore.txt 2>&1
 cp $OUT/evidence_cevae_b16.json $P/r05_evidence_cevae_b16.json; cp $OUT/evidence_gmvae_restore_b16.json $P/r05_evidence_gmvae_restore_b16.json
 # ---- SQ counters of the default mode
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $OUT/sq_insts -- python $REPO/bench.py --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_insts.err || true
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/sq_cycles -- python $REPO/bench.py --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_cycles.err || true
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $OUT/sq_insts -- python $REPO/bench.py --full --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_insts.err || true
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/sq_cycles -- python $REPO/bench.py --full --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_cycles.err || true
 python - "$OUT" <<'PY'
 import sys, glob, csv, collections
 out = sys.argv[1]
@@ -51,11 +51,11 @@ find $OUT -name "*kernel_trace.csv" -delete; find $OUT -name "*counter_collectio
 rm -rf $OUT/stats_* $OUT/fetch_* $OUT/write_* $OUT/sq_insts $OUT/sq_cycles 2>/dev/null
 cd $REPO
 # ---- the bench lines (they read the files written above)
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 timeout 300 python bench.py --arch ceVAE --no-cpu-baseline > $OUT/bench_cevae_b16.json 2> $OUT/bench_cevae.err
 timeout 600 python bench.py --arch GMVAE_spatial --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_gmvae_restore.json 2> $OUT/bench_gmvae.err
 timeout 600 python bench.py --arch fAnoGAN --variant resnet --steps 5 --warmup 2 > $OUT/bench_fanogan_resnet64.json 2> $OUT/bench_fanogan.err
-GPU_MAX_HW_QUEUES=8 UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 100 --warmup 10 --quick --no-cpu-baseline > $OUT/bench_nccl1.json 2> $OUT/bench_nccl1.err
+GPU_MAX_HW_QUEUES=8 UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --steps 100 --warmup 10 --quick --no-cpu-baseline > $OUT/bench_nccl1.json 2> $OUT/bench_nccl1.err
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -15 > $OUT/pytest_gpu_full.log
 fi

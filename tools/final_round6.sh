@@ -14,10 +14,10 @@ ONLY=${ONLY:-"vae cevae gmvae fanogan sq"}
 cd /tmp
 prof3() {   # prof3 <tag> <bench args...>: stats + FETCH_SIZE + WRITE_SIZE passes of one bench command (PMC passes with --kernel-trace only)
   tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$tag -- python $REPO/bench.py "$@" > $OUT/${tag}_bench_under_profiler.json 2>$OUT/stats_$tag.err || true
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$tag -- python $REPO/bench.py --full "$@" > $OUT/${tag}_bench_under_profiler.json 2>$OUT/stats_$tag.err || true
   find $OUT/stats_$tag -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${tag}_kernel_stats.csv
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$tag -- python $REPO/bench.py "$@" > /dev/null 2>$OUT/fetch_$tag.err || true
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write_$tag -- python $REPO/bench.py "$@" > /dev/null 2>$OUT/write_$tag.err || true
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch_$tag -- python $REPO/bench.py --full "$@" > /dev/null 2>$OUT/fetch_$tag.err || true
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write_$tag -- python $REPO/bench.py --full "$@" > /dev/null 2>$OUT/write_$tag.err || true
 }
 has() { case " $ONLY " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has vae; then
@@ -48,8 +48,8 @@ if has fanogan; then
 fi
 if has sq; then
   # ---- SQ counters of the default mode (instruction mix per kernel: VALU per MFMA) and of bf16x6
-  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $OUT/sq_insts -- python $REPO/bench.py --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_insts.err || true
-  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/sq_cycles -- python $REPO/bench.py --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_cycles.err || true
+  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $OUT/sq_insts -- python $REPO/bench.py --full --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_insts.err || true
+  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM --output-format csv -d $OUT/sq_cycles -- python $REPO/bench.py --full --steps 2 --warmup 1 --rounds 1 $Q > /dev/null 2>$OUT/sq_cycles.err || true
   python - "$OUT" <<'PY'
 import sys, glob, csv, collections
 out = sys.argv[1]
@@ -71,12 +71,12 @@ rm -rf $OUT/stats_* $OUT/fetch_* $OUT/write_* $OUT/sq_insts $OUT/sq_cycles 2>/de
 cd $REPO
 [ "${NO_BENCH:-0}" = "1" ] && { ls $OUT; head -12 $OUT/pmc_sq_insts.csv 2>/dev/null; head -30 $OUT/fanogan_resnet64_kernel_stats.csv 2>/dev/null | cut -c1-200; exit 0; }
 # ---- the bench lines (they read the files written above)
-timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 timeout 300 python bench.py --arch ceVAE --no-cpu-baseline > $OUT/bench_cevae_b16.json 2> $OUT/bench_cevae.err
 timeout 600 python bench.py --arch GMVAE_spatial --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_gmvae_restore.json 2> $OUT/bench_gmvae.err
 timeout 600 python bench.py --arch GMVAE_spatial --volume --steps 3 --warmup 1 > $OUT/bench_gmvae_volume.json 2> $OUT/bench_gmvae_volume.err
 timeout 600 python bench.py --arch fAnoGAN --variant resnet --steps 5 --warmup 2 > $OUT/bench_fanogan_resnet64.json 2> $OUT/bench_fanogan.err
-GPU_MAX_HW_QUEUES=8 UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 100 --warmup 10 --quick --no-cpu-baseline > $OUT/bench_nccl1.json 2> $OUT/bench_nccl1.err
+GPU_MAX_HW_QUEUES=8 UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --steps 100 --warmup 10 --quick --no-cpu-baseline > $OUT/bench_nccl1.json 2> $OUT/bench_nccl1.err
 timeout 300 python tools/eval_bench.py > $OUT/eval_bench.txt 2> $OUT/eval_bench.err
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 2400 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -15 > $OUT/pytest_gpu_full.log

@@ -9,7 +9,7 @@ OUT=$PWD/gpurun_out/pmc_$TAG
 rm -rf $OUT; mkdir -p $OUT
 REPO=$PWD
 cd /tmp
-rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1 || true
+rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > $OUT/bench.log 2>&1 || true
 cd $REPO
 python - "$OUT" <<'PY'
 import sys, glob, csv, collections

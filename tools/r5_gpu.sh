@@ -8,10 +8,10 @@ Q="--quick --no-cpu-baseline"
 case $STEP in
 a)  # verdict item 1, step A: issue-port micro-benchmark, shader clock under load, phase clocks of the dec3 filter gradient and of dec3.fwd, same-box baseline
     timeout 120 tools/issue_ubench > $OUT/issue_ubench.log 2>&1
-    UAD_DBG=160 timeout 200 python bench.py --steps 5 --warmup 2 --rounds 1 $Q > $OUT/w_tr_phase.json 2> $OUT/w_tr_phase.log
-    UAD_DBG=64 timeout 200 python bench.py --steps 20 --warmup 30 --rounds 1 $Q > $OUT/d16s_phase.json 2> $OUT/d16s_phase.log
-    timeout 200 python bench.py --steps 50 --warmup 10 $Q > $OUT/bench_bf16x3.json 2> $OUT/bench_bf16x3.err
-    timeout 200 python bench.py --steps 30 --warmup 10 --math f32 $Q > $OUT/bench_f32.json 2> $OUT/bench_f32.err
+    UAD_DBG=160 timeout 200 python bench.py --full --steps 5 --warmup 2 --rounds 1 $Q > $OUT/w_tr_phase.json 2> $OUT/w_tr_phase.log
+    UAD_DBG=64 timeout 200 python bench.py --full --steps 20 --warmup 30 --rounds 1 $Q > $OUT/d16s_phase.json 2> $OUT/d16s_phase.log
+    timeout 200 python bench.py --full --steps 50 --warmup 10 $Q > $OUT/bench_bf16x3.json 2> $OUT/bench_bf16x3.err
+    timeout 200 python bench.py --full --steps 30 --warmup 10 --math f32 $Q > $OUT/bench_f32.json 2> $OUT/bench_f32.err
     cat $OUT/issue_ubench.log; grep -h "w5 CB\|wg0 w0\|wg5 w3\|wg10 w6" $OUT/w_tr_phase.log | head -40; grep -h "d16s wg" $OUT/d16s_phase.log | head -8
     python - <<'PY'
 import json
@@ -32,8 +32,8 @@ b)  # f32 pipelined filter gradient (parity: same bits as the round-2 kernel) + 
     timeout 600 python -m pytest tests/test_gpu_model.py -m gpu -q -x -p no:cacheprovider 2>&1 | tail -5 > $OUT/pytest_model.log
     cat $OUT/pytest_model.log
     for r in 1 2; do
-      UAD_NO_W_F32P=1 timeout 200 python bench.py --steps 30 --warmup 5 --math f32 $Q > $OUT/f32_old_$r.json 2>/dev/null
-      timeout 200 python bench.py --steps 30 --warmup 5 --math f32 $Q > $OUT/f32_new_$r.json 2>/dev/null
+      UAD_NO_W_F32P=1 timeout 200 python bench.py --full --steps 30 --warmup 5 --math f32 $Q > $OUT/f32_old_$r.json 2>/dev/null
+      timeout 200 python bench.py --full --steps 30 --warmup 5 --math f32 $Q > $OUT/f32_new_$r.json 2>/dev/null
     done
     python - <<'PY'
 import json, glob
@@ -49,7 +49,7 @@ c)  # A/B of two library builds: ablibs/libA.so (before) vs the tree's (after); 
     [ -n "$TESTS" ] && { UAD_MATH=bf16x3 timeout 900 python -m pytest $TESTS -m gpu -q -x -p no:cacheprovider 2>&1 | tail -4; }
     for r in 1 2 3; do for v in A B; do for m in ${MODES:-bf16x3}; do
       L=$PWD/ablibs/libA.so; [ $v = B ] && L=${LIBB:-$PWD/unsupervised_anomaly_detection_brain_mri_amd/libuad_hip.so}
-      UAD_LIB=$L timeout 200 python bench.py --steps 40 --warmup 5 --math $m $Q > $OUT/${m}_${v}_$r.json 2>/dev/null
+      UAD_LIB=$L timeout 200 python bench.py --full --steps 40 --warmup 5 --math $m $Q > $OUT/${m}_${v}_$r.json 2>/dev/null
     done; done; done
     python tools/ab_table.py $OUT $TAGS
     ;;
@@ -57,13 +57,13 @@ e)  # same-box A/B of two ENVIRONMENTS on the tree's library: ENVA="K=V .." ENVB
     [ -n "$TESTS" ] && timeout 900 python -m pytest $TESTS -m gpu -q -x -p no:cacheprovider 2>&1 | tail -4
     for r in 1 2 3; do for v in A B; do for m in ${MODES:-bf16x3}; do
       E="$ENVA"; [ $v = B ] && E="$ENVB"
-      env $E timeout 200 python bench.py --steps 40 --warmup 5 --math $m $Q > $OUT/${m}_${v}_$r.json 2>/dev/null
+      env $E timeout 200 python bench.py --full --steps 40 --warmup 5 --math $m $Q > $OUT/${m}_${v}_$r.json 2>/dev/null
     done; done; done
     echo "A: $ENVA | B: $ENVB"
     python tools/ab_table.py $OUT
     ;;
 f)  # phase clocks of the filter-gradient kernel of the given math mode:  MODE=f32 bash tools/r5_gpu.sh f
-    UAD_DBG=160 timeout 200 python bench.py --steps 5 --warmup 2 --rounds 1 --math ${MODE:-f32} $Q > $OUT/phase.json 2> $OUT/phase.log
+    UAD_DBG=160 timeout 200 python bench.py --full --steps 5 --warmup 2 --rounds 1 --math ${MODE:-f32} $Q > $OUT/phase.json 2> $OUT/phase.log
     grep -h "w5 CB\|wg0 w\|wg5 w\|wg10 w" $OUT/phase.log | head -60
     ;;
 g)  # library-issued RCCL on one rank: step time of the plain step, the torch process-group path and the library path (own stream / side stream), same box
@@ -72,11 +72,11 @@ g)  # library-issued RCCL on one rank: step time of the plain step, the torch pr
     UAD_AR_STREAM=side timeout 300 python tools/host_time_dp.py 2>&1 | grep "library RCCL\|plain" > $OUT/rccl_side_stream.log; cat $OUT/rccl_side_stream.log
     UAD_AR_SKIP=1 timeout 300 python tools/host_time_dp.py 2>&1 | grep "library RCCL\|plain" > $OUT/rccl_own_stream_skip.log; echo "UAD_AR_SKIP=1 (everything but the ncclAllReduce call):"; cat $OUT/rccl_own_stream_skip.log
     UAD_AR_SKIP=1 UAD_AR_STREAM=side timeout 300 python tools/host_time_dp.py 2>&1 | grep "library RCCL\|plain" > $OUT/rccl_side_stream_skip.log; cat $OUT/rccl_side_stream_skip.log
-    UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 50 --warmup 10 $Q > $OUT/bench_nccl1.json 2> $OUT/bench_nccl1.err
+    UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --steps 50 --warmup 10 $Q > $OUT/bench_nccl1.json 2> $OUT/bench_nccl1.err
     python -c "import json; d = json.load(open('$OUT/bench_nccl1.json')); print(d['ms_per_step'], d['value'], json.dumps(d.get('allreduce'))[:600])"
     ;;
 h)  # bench.py's N > 1 path under RCCL on one rank (UAD_BENCH_REHEARSAL=nccl1): torch path, library path, and orderings / queue counts of the library path
-    run1() { tag=$1; shift; env "$@" UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 50 --warmup 10 $Q > $OUT/$tag.json 2> $OUT/$tag.err
+    run1() { tag=$1; shift; env "$@" UAD_BENCH_REHEARSAL=nccl1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --steps 50 --warmup 10 $Q > $OUT/$tag.json 2> $OUT/$tag.err
       python -c "import json; s = open('$OUT/$tag.json').read(); d = json.loads(s[s.index('{'):]); a = d['allreduce']; print('$tag', 'stdout clean' if s.lstrip().startswith('{') else 'STDOUT POLLUTED', d['ms_per_step'], 'without all-reduce', a['ms_per_step_without_allreduce'], 'exposed', a['exposed_comm_ms'])"; }
     run1 torch_pg UAD_DP_LIBRARY_AR=0
     run1 library UAD_X=0

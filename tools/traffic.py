@@ -1,5 +1,5 @@
 """Post-processes two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; each with --kernel-trace only) of
-`bench.py --steps 2 --warmup 1 --no-cpu-baseline` into
+`bench.py --full --steps 2 --warmup 1 --no-cpu-baseline` into
   * a per-(kernel, grid) table (stdout / profiles/*.md), and
   * profiles/r0N_traffic_<math>.json, keyed by bench.py's launch-group tags for the big conv kernels
     (tag <-> (kernel template, grid) at the BASELINE configs[1] shapes, N = 64).
