@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/uad_hip.h"
+#include "uad_allreduce.h"
 #include "uad_kernels.h"
 
 int uad_fail(int code, const char* fmt, ...);
@@ -71,12 +72,11 @@ struct uad_gan {
     int math;
     bool packed_valid;
     // library-issued, bucketed gradient all-reduce of a phase's trained group (uad_gan_allreduce_attach, round 6): the group's tensors are cut into up to four
-    // contiguous buckets; a bucket's ncclAllReduce is enqueued on ar_stream as soon as the LAST kernel that writes one of its tensors is enqueued
-    // (gan_grad_final marks a tensor; the pending count of its bucket reaching zero issues it), i.e. while the backward of the earlier layers still runs
-    void* ar_comm; int ar_world;
-    hipStream_t ar_stream; hipEvent_t ar_ev_in[4], ar_ev_out;
-    struct ArBucket { long long off, cnt; int pending; bool issued; } ar_b[4];
-    int ar_nb; bool ar_active; hipStream_t ar_st;
+    // contiguous buckets of the lane; a bucket's collective is enqueued on the lane's stream as soon as the LAST kernel that writes one of its tensors is
+    // enqueued (gan_grad_final marks a tensor; the pending count of its bucket reaching zero issues it), i.e. while the backward of the earlier layers still runs
+    UadArLane ar;
+    struct ArBucket { int pending; bool issued; } ar_b[4];
+    bool ar_active; hipStream_t ar_st; int ar_err;      // ar_err: the phase's first failed issue (later buckets are not issued)
     std::vector<std::pair<long long, int>> ar_tb;      // (tensor offset, bucket) of the trained group's tensors, and whether it was marked
     std::vector<char> ar_marked;
     bool pack_all; long long dirty_lo, dirty_hi;      // which parameters changed since the last pack: everything, or [dirty_lo, dirty_hi) (an optimizer step touches ONE group)
@@ -167,31 +167,29 @@ float* Gr(uad_gan* m, long long off) { return m->grads + off; }
 // ---- bucketed all-reduce of the trained group's gradients (data parallelism, library-issued RCCL) --------------------------------------------
 static void gan_ar_issue(uad_gan* m, int b) {
     uad_gan::ArBucket& B = m->ar_b[b];
-    if (B.issued || B.cnt == 0) { B.issued = true; return; }
+    if (B.issued) return;
     B.issued = true;
-    (void)hipEventRecord(m->ar_ev_in[b], m->ar_st);                 // behind the kernels that wrote the bucket's tensors ...
-    (void)hipStreamWaitEvent(m->ar_stream, m->ar_ev_in[b], 0);
-    static const bool skip = getenv("UAD_AR_SKIP") != nullptr;      // measurement: everything but the collective itself
-    if (!skip) (void)uad_rccl_allreduce(m->ar_comm, m->grads + B.off, B.cnt, m->ar_stream);      // ... on the collective stream: the phase's stream runs on
+    // behind the kernels that wrote the bucket's tensors, on the lane's stream: the phase's stream runs on
+    if (m->ar.cnt[b] > 0 && m->ar_err == UAD_OK) m->ar_err = uad_ar_issue(&m->ar, b, m->ar_st);
 }
 // phase start: buckets over the tensors inside [off, off + cnt), by cumulative size, on tensor boundaries, in offset order
 static void gan_ar_begin(uad_gan* m, long long off, long long cnt, hipStream_t st) {
     m->ar_active = false;
-    if (!m->ar_comm || cnt <= 0) return;
+    if (!m->ar.comm || cnt <= 0) return;
     std::vector<const Tensor*> ts;
     for (const Tensor& t : m->tensors) if (t.off >= off && t.off + t.count() <= off + cnt) ts.push_back(&t);
     std::sort(ts.begin(), ts.end(), [](const Tensor* a, const Tensor* b) { return a->off < b->off; });
     constexpr int K = 4;
-    m->ar_nb = K; m->ar_tb.clear(); m->ar_marked.assign(ts.size(), 0);
-    for (int b = 0; b < K; ++b) m->ar_b[b] = {0, 0, 0, false};
+    m->ar.nb = K; m->ar_tb.clear(); m->ar_marked.assign(ts.size(), 0);
+    for (int b = 0; b < K; ++b) { m->ar_b[b] = {0, false}; m->ar.off[b] = m->ar.cnt[b] = 0; }
     long long cum = 0;
     for (const Tensor* t : ts) {
         int b = (int)((cum + t->count() / 2) * K / cnt);
         if (b >= K) b = K - 1;
         cum += t->count();
         uad_gan::ArBucket& B = m->ar_b[b];
-        if (B.pending == 0) B.off = t->off;
-        B.cnt = t->off + t->count() - B.off;
+        if (B.pending == 0) m->ar.off[b] = t->off;
+        m->ar.cnt[b] = t->off + t->count() - m->ar.off[b];
         B.pending += 1;
         m->ar_tb.push_back({t->off, b});
     }
@@ -199,12 +197,13 @@ static void gan_ar_begin(uad_gan* m, long long off, long long cnt, hipStream_t s
     int prev = -1;
     for (int b = 0; b < K; ++b) {
         if (m->ar_b[b].pending == 0) continue;
-        if (prev < 0) { m->ar_b[b].cnt += m->ar_b[b].off - off; m->ar_b[b].off = off; }
-        else m->ar_b[prev].cnt = m->ar_b[b].off - m->ar_b[prev].off;
+        if (prev < 0) { m->ar.cnt[b] += m->ar.off[b] - off; m->ar.off[b] = off; }
+        else m->ar.cnt[prev] = m->ar.off[b] - m->ar.off[prev];
         prev = b;
     }
-    if (prev >= 0) m->ar_b[prev].cnt = off + cnt - m->ar_b[prev].off;
+    if (prev >= 0) m->ar.cnt[prev] = off + cnt - m->ar.off[prev];
     m->ar_st = st;
+    m->ar_err = UAD_OK;
     m->ar_active = prev >= 0;
 }
 // the kernels that write the gradient of the tensor at `off` are enqueued and nothing later in this phase writes it again
@@ -218,14 +217,15 @@ void gan_grad_final(uad_gan* m, long long off) {
         return;
     }
 }
-// phase end: whatever was not marked (zero gradients that stay at their initialisation, graphs without hooks) goes now; the phase's stream -- the
-// optimizer step comes next on it -- waits for the collective stream once
-static void gan_ar_end(uad_gan* m) {
-    if (!m->ar_active) return;
-    for (int b = 0; b < m->ar_nb; ++b) if (!m->ar_b[b].issued) gan_ar_issue(m, b);
-    (void)hipEventRecord(m->ar_ev_out, m->ar_stream);
-    (void)hipStreamWaitEvent(m->ar_st, m->ar_ev_out, 0);
+// phase end: whatever was not marked (zero gradients that stay at their initialisation, graphs without hooks) goes now, unless an issue or the phase
+// itself (rc) failed; the phase's stream -- the optimizer step comes next on it -- waits once for the collectives that were issued.  Returns the first error.
+static int gan_ar_end(uad_gan* m, int rc) {
+    if (!m->ar_active) return rc;
+    if (m->ar_err == UAD_OK) m->ar_err = rc;
+    for (int b = 0; b < m->ar.nb; ++b) gan_ar_issue(m, b);
+    const int jr = uad_ar_join(&m->ar, m->ar_st);
     m->ar_active = false;
+    return m->ar_err != UAD_OK ? m->ar_err : jr;
 }
 const float* PKF(uad_gan* m, long long off) { return m->math == UAD_MATH_F32 ? m->wpack_f + off : nullptr; }
 const float* PKD(uad_gan* m, long long off) { return m->math == UAD_MATH_F32 ? m->wpack_d + off : nullptr; }
@@ -1570,9 +1570,10 @@ extern "C" {
 
 int uad_gan_destroy(uad_gan_t* m) {
     if (!m) return UAD_OK;
+    const int rc = uad_ar_close(&m->ar);      // (waits for a collective still queued on the lane's stream: it reads `grads`)
     for (void* p : m->allocs) hipFree(p);
     delete m;
-    return UAD_OK;
+    return rc;
 }
 long long uad_gan_param_count(const uad_gan_t* m) { return m ? m->nparams : 0; }
 int uad_gan_num_tensors(const uad_gan_t* m) { return m ? (int)m->tensors.size() : 0; }
@@ -1861,36 +1862,27 @@ int uad_gan_restore_step(uad_gan_t* m, float* x_restored, const uad_gan_io_t* io
 
 int uad_gan_phase(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n, int want_backward, void* stream) {
     if (!m || !io) return fail(UAD_ERR_INVALID, "null argument");
-    if (m->ar_comm && want_backward && phase >= 0 && phase <= 2 && m->variant != UAD_GAN_AAE) {
+    if (m->ar.comm && want_backward && phase >= 0 && phase <= 2 && m->variant != UAD_GAN_AAE) {
         // data parallelism, library-issued: the trained group's slice (AnoVAE-GAN's Encoder phase trains Encoder + Generator, one contiguous slice)
         long long off = m->grp_off[phase], cnt = m->grp_cnt[phase];
         if (m->variant == UAD_GAN_ANOVAEGAN && phase == UAD_GAN_ENCODER) { off = 0; cnt = m->grp_cnt[UAD_GAN_ENCODER] + m->grp_cnt[UAD_GAN_GENERATOR]; }
         gan_ar_begin(m, off, cnt, (hipStream_t)stream);
     }
-    const int rc = gan_phase_body(m, phase, io, n, want_backward, stream);
-    if (rc == UAD_OK) gan_ar_end(m); else m->ar_active = false;
-    return rc;
+    return gan_ar_end(m, gan_phase_body(m, phase, io, n, want_backward, stream));
 }
 // Attaches an RCCL communicator (uad_rccl_comm_create) to the handle: from then on uad_gan_phase(..., want_backward) all-reduces the trained group's
 // gradient slice itself, in up to four buckets issued on a collective stream while the phase's backward still runs; the phase's stream waits for the last
 // one before it returns to the caller (whose next launch is uad_gan_adam with grad_scale = 1 / world).  comm = NULL detaches.  The AAE-family graphs have no
-// bucket hooks: UAD_ERR_UNSUPPORTED, the caller all-reduces their slice itself (uad_rccl_allreduce).
+// bucket hooks: UAD_ERR_UNSUPPORTED, the caller all-reduces their slice itself.
 int uad_gan_allreduce_attach(uad_gan_t* m, void* comm, int world) {
     if (!m) return fail(UAD_ERR_INVALID, "null handle");
-    if (!comm) { m->ar_comm = nullptr; m->ar_world = 1; m->ar_active = false; return UAD_OK; }
+    if (!comm) { m->ar.comm = nullptr; m->ar.world = 1; m->ar_active = false; return UAD_OK; }
     if (world < 1) return fail(UAD_ERR_INVALID, "uad_gan_allreduce_attach: world %d", world);
     if (m->variant == UAD_GAN_AAE) return fail(UAD_ERR_UNSUPPORTED, "uad_gan_allreduce_attach: the AAE-family phases are all-reduced by the caller");
-    if (!m->ar_stream) {
-        // HIGH-priority, non-blocking.  Measured on one rank under RCCL with GPU_MAX_HW_QUEUES=8 (the package's multi-process default): a normal-priority
-        // stream here made the WGAN iteration 1.62x the plain one (83 vs 51 ms) WITH OR WITHOUT the collectives being issued -- the extra stream's hardware
-        // queue, not RCCL; a blocking stream 2.2x; the high-priority stream 1.016x, as do 4-6 hardware queues (profiles/r06_e_gan_dp_one_rank.md).
-        { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); HIP_TRY(hipStreamCreateWithPriority(&m->ar_stream, hipStreamNonBlocking, hi)); }
-        for (int i = 0; i < 4; ++i)
-            if (hipEventCreateWithFlags(&m->ar_ev_in[i], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) HIP_TRY(hipEventCreateWithFlags(&m->ar_ev_in[i], hipEventDisableTiming));
-        if (hipEventCreateWithFlags(&m->ar_ev_out, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) HIP_TRY(hipEventCreateWithFlags(&m->ar_ev_out, hipEventDisableTiming));
-    }
-    m->ar_comm = comm; m->ar_world = world;
-    return UAD_OK;
+    // HIGH-priority, non-blocking.  Measured on one rank under RCCL with GPU_MAX_HW_QUEUES=8 (the package's multi-process default): a normal-priority
+    // stream here made the WGAN iteration 1.62x the plain one (83 vs 51 ms) WITH OR WITHOUT the collectives being issued -- the extra stream's hardware
+    // queue, not RCCL; a blocking stream 2.2x; the high-priority stream 1.016x, as do 4-6 hardware queues (profiles/r06_e_gan_dp_one_rank.md).
+    return uad_ar_open(&m->ar, comm, world, m->grads, UAD_AR_OWN_HIGH, nullptr);
 }
 int uad_gan_reconstruct(uad_gan_t* m, const uad_gan_io_t* io, int n, void* stream) {
     if (!m || !io) return fail(UAD_ERR_INVALID, "null argument");

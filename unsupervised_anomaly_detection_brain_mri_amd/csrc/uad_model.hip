@@ -14,20 +14,9 @@
 #include <string>
 #include <vector>
 
-#include <dlfcn.h>
 #include <unistd.h>
-// RCCL: types only -- the library is bound at run time (rccl_api below), libuad_hip.so does not link it.  Without the development header (a single-GPU ROCm
-// install) the few opaque types are declared here and the uad_rccl_* entry points still work whenever librccl.so.1 itself can be loaded.
-#if __has_include(<rccl/rccl.h>)
-#include <rccl/rccl.h>
-#else
-typedef struct ncclComm* ncclComm_t;
-typedef struct { char internal[128]; } ncclUniqueId;
-typedef enum { ncclSuccess = 0 } ncclResult_t;
-typedef enum { ncclInt8 = 0, ncclChar = 0, ncclUint8 = 1, ncclInt32 = 2, ncclInt = 2, ncclUint32 = 3, ncclInt64 = 4, ncclUint64 = 5, ncclFloat16 = 6, ncclHalf = 6, ncclFloat32 = 7, ncclFloat = 7, ncclFloat64 = 8, ncclDouble = 8 } ncclDataType_t;
-typedef enum { ncclSum = 0, ncclProd = 1, ncclMax = 2, ncclMin = 3, ncclAvg = 4 } ncclRedOp_t;
-#endif
 #include "../../include/uad_hip.h"
+#include "uad_allreduce.h"
 #include "uad_kernels.h"
 
 static thread_local std::string g_err;
@@ -141,10 +130,9 @@ struct uad_model {
     bool joined;                       // uad_backward_deferred: the segment just run ended with the side stream joined into the caller's
     bool last_fused_final;             // the last forward ran the last block's BN / final conv / loss inside the ConvT epilogue (its c is not written)
     std::vector<void*> allocs;
-    // library-issued gradient all-reduce (uad_allreduce_attach): RCCL communicator of this rank, the stream the collectives run on, the bucket plan
-    void* ar_comm; int ar_world; hipStream_t ar_stream; bool ar_own_stream;
-    int ar_nb; int ar_after[4]; long long ar_off[4], ar_cnt[4];
-    hipEvent_t ar_ev_in[4], ar_ev_out; bool ar_pending;
+    // library-issued gradient all-reduce (uad_allreduce_attach): the lane, and after which backward segment each of its buckets is issued
+    UadArLane ar;
+    int ar_after[4];
     // second stream + events of the backward pass; per-layer scratch touched by that stream
     hipStream_t side;
     std::vector<hipEvent_t> sync_events;
@@ -311,8 +299,6 @@ int uad_create(const uad_config_t* cfg, uad_model_t** out) {
     m->step = 0;
     m->have_fwd = false;
     m->prof_on = false;
-    m->ar_comm = nullptr; m->ar_world = 1; m->ar_stream = nullptr; m->ar_own_stream = false; m->ar_nb = 0; m->ar_ev_out = nullptr; m->ar_pending = false;
-    for (int i = 0; i < 4; ++i) m->ar_ev_in[i] = nullptr;
     const int npool = ilog2i(H) - ilog2i(cfg->inter_res);
     m->n_pool = npool;
     if (npool < 1 || npool > 7) { delete m; return fail(UAD_ERR_UNSUPPORTED, "log2(height/inter_res) = %d: 1..7 conv blocks supported", npool); }
@@ -530,18 +516,16 @@ int uad_create(const uad_config_t* cfg, uad_model_t** out) {
 
 int uad_destroy(uad_model_t* m) {
     if (!m) return UAD_OK;
+    const int rc = uad_ar_close(&m->ar);
     for (void* p : m->allocs) hipFree(p);
     for (hipEvent_t e : m->sync_events) (void)hipEventDestroy(e);
     if (m->ev_opt) (void)hipEventDestroy(m->ev_opt);
     if (m->ev_pack) (void)hipEventDestroy(m->ev_pack);
     if (m->ev_pack_head) (void)hipEventDestroy(m->ev_pack_head);
-    for (int i = 0; i < 4; ++i) if (m->ar_ev_in[i]) (void)hipEventDestroy(m->ar_ev_in[i]);
-    if (m->ar_ev_out) (void)hipEventDestroy(m->ar_ev_out);
-    if (m->ar_own_stream && m->ar_stream) (void)hipStreamDestroy(m->ar_stream);
     if (m->side) (void)hipStreamDestroy(m->side);
     if (m->bott_err_host) (void)hipHostFree(m->bott_err_host);
     delete m;
-    return UAD_OK;
+    return rc;
 }
 
 long long uad_param_count(const uad_model_t* m) { return m ? m->nparams : 0; }
@@ -1299,99 +1283,14 @@ int uad_backward_deferred(uad_model_t* m, int segment, void* stream, void** read
     return rc;
 }
 
-// ------------------------------------------------------------------------------------------------ library-issued RCCL all-reduce
-// RCCL is bound at run time: librccl.so.1 as the process already has it (the copy PyTorch-ROCm loads), else from the loader path.  libuad_hip.so
-// itself has no link-time dependency on it -- single-GPU users and the CPU-side symbol tests never touch it.
-namespace {
-struct RcclApi {
-    void* h = nullptr;
-    decltype(&ncclGetUniqueId) getUniqueId = nullptr;
-    decltype(&ncclCommInitRank) commInitRank = nullptr;
-    decltype(&ncclCommDestroy) commDestroy = nullptr;
-    decltype(&ncclAllReduce) allReduce = nullptr;
-    decltype(&ncclGetErrorString) errString = nullptr;
-    bool ok = false;
-};
-RcclApi* rccl_api() {
-    static RcclApi api;
-    static bool tried = false;
-    if (tried) return api.ok ? &api : nullptr;
-    tried = true;
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    if (const char* over = getenv("UAD_RCCL_LIB")) api.h = dlopen(over, RTLD_NOW | RTLD_LOCAL);      // explicit override wins (tests: a stub whose "all-reduce" doubles)
-    for (const char* nm : names) {
-        if (api.h) break;
-        api.h = dlopen(nm, RTLD_NOW | RTLD_NOLOAD | RTLD_GLOBAL);       // the copy the process already uses (torch's), if any
-    }
-    for (const char* nm : names) {
-        if (api.h) break;
-        api.h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
-    }
-    if (!api.h) return nullptr;
-    api.getUniqueId = reinterpret_cast<decltype(api.getUniqueId)>(dlsym(api.h, "ncclGetUniqueId"));
-    api.commInitRank = reinterpret_cast<decltype(api.commInitRank)>(dlsym(api.h, "ncclCommInitRank"));
-    api.commDestroy = reinterpret_cast<decltype(api.commDestroy)>(dlsym(api.h, "ncclCommDestroy"));
-    api.allReduce = reinterpret_cast<decltype(api.allReduce)>(dlsym(api.h, "ncclAllReduce"));
-    api.errString = reinterpret_cast<decltype(api.errString)>(dlsym(api.h, "ncclGetErrorString"));
-    api.ok = api.getUniqueId && api.commInitRank && api.commDestroy && api.allReduce && api.errString;
-    return api.ok ? &api : nullptr;
-}
-#define RCCL_API(A)                                                                                                         \
-    RcclApi* A = rccl_api();                                                                                                \
-    if (!A) return fail(UAD_ERR_UNSUPPORTED, "librccl.so.1 could not be loaded or lacks the nccl* entry points (set UAD_RCCL_LIB to its path)")
-#define RCCL_TRY(A, expr)                                                                              \
-    do {                                                                                               \
-        ncclResult_t r_ = (expr);                                                                      \
-        if (r_ != ncclSuccess) return fail(UAD_ERR_HIP, "%s failed: %s", #expr, (A)->errString(r_));   \
-    } while (0)
-}  // namespace
-
-int uad_rccl_unique_id(void* id_out, int cap) {
-    if (!id_out || cap < (int)sizeof(ncclUniqueId)) return fail(UAD_ERR_INVALID, "uad_rccl_unique_id: need a buffer of %d bytes", (int)sizeof(ncclUniqueId));
-    RCCL_API(api);
-    ncclUniqueId id;
-    RCCL_TRY(api, api->getUniqueId(&id));
-    memcpy(id_out, &id, sizeof id);
-    return UAD_OK;
-}
-int uad_rccl_comm_create(const void* id_bytes, int world, int rank, void** comm_out) {
-    if (!id_bytes || !comm_out || world < 1 || rank < 0 || rank >= world) return fail(UAD_ERR_INVALID, "uad_rccl_comm_create: bad arguments");
-    RCCL_API(api);
-    ncclUniqueId id;
-    memcpy(&id, id_bytes, sizeof id);
-    ncclComm_t c = nullptr;
-    // (RCCL prints a start-up banner -- version / host / library path -- to STDOUT from rank 0's first communicator.  A caller whose stdout is a protocol
-    // points its file descriptor 1 elsewhere itself, as bench.py's claim_stdout() does: the library does not touch process-wide descriptors -- ADVICE r5.)
-    const ncclResult_t r = api->commInitRank(&c, world, id, rank);        // collective over the ranks: every rank calls it with rank 0's id, on its own device
-    if (r != ncclSuccess) return fail(UAD_ERR_HIP, "ncclCommInitRank failed: %s", api->errString(r));
-    *comm_out = (void*)c;
-    return UAD_OK;
-}
-int uad_rccl_comm_destroy(void* comm) {
-    if (!comm) return UAD_OK;
-    RCCL_API(api);
-    RCCL_TRY(api, api->commDestroy((ncclComm_t)comm));
-    return UAD_OK;
-}
-int uad_rccl_allreduce(void* comm, float* buf, long long count, void* stream) {
-    if (!comm || !buf || count <= 0) return fail(UAD_ERR_INVALID, "uad_rccl_allreduce: bad arguments");
-    RCCL_API(api);
-    RCCL_TRY(api, api->allReduce(buf, buf, (size_t)count, ncclFloat, ncclSum, (ncclComm_t)comm, (hipStream_t)stream));
-    return UAD_OK;
-}
-
+// ------------------------------------------------------------------------------------------------ library-issued RCCL all-reduce (uad_allreduce.hip)
 int uad_allreduce_attach(uad_model_t* m, void* comm, int world, int nbuckets, const int* after_segment, const long long* offset, const long long* count) {
     if (!m) return fail(UAD_ERR_INVALID, "null model");
-    if (!comm) { m->ar_comm = nullptr; m->ar_world = 1; m->ar_nb = 0; return UAD_OK; }      // detach
+    if (!comm) { m->ar.comm = nullptr; m->ar.world = 1; m->ar.nb = 0; return UAD_OK; }      // detach
     if (world < 1 || nbuckets < 1 || nbuckets > 4 || !after_segment || !offset || !count) return fail(UAD_ERR_INVALID, "uad_allreduce_attach: 1..4 buckets");
-    RCCL_API(api);
-    (void)api;
-    for (int i = 0; i < nbuckets; ++i) {
+    for (int i = 0; i < nbuckets; ++i)
         if (after_segment[i] < UAD_SEG_DECODER || after_segment[i] > UAD_SEG_ENCODER_LO || offset[i] < 0 || count[i] < 0 || offset[i] + count[i] > m->nparams)
             return fail(UAD_ERR_INVALID, "uad_allreduce_attach: bucket %d (after segment %d, [%lld, +%lld)) outside the gradient buffer", i, after_segment[i], offset[i], count[i]);
-        m->ar_after[i] = after_segment[i]; m->ar_off[i] = offset[i]; m->ar_cnt[i] = count[i];
-    }
-    m->ar_nb = nbuckets; m->ar_comm = comm; m->ar_world = world;
     // Default: the collectives of the deferred segments are enqueued on the handle's SIDE stream, right behind the slab reductions that complete
     // their bucket -- no event at all; the last bucket goes onto the caller's stream in front of the optimizer step.  Measured on one rank under RCCL
     // (profiles/r05_d_rccl_one_rank.log): the step costs what the plain step costs (0.822 vs 0.822 ms; torch.distributed's path 0.858).
@@ -1399,62 +1298,46 @@ int uad_allreduce_attach(uad_model_t* m, void* comm, int world, int nbuckets, co
     // not the default because a third stream per handle makes the step depend on how HIP maps streams to hardware queues: bench.py's own N > 1
     // path read 1.54 ms per step with it (0.87 on the side stream) where tools/host_time_dp.py, creating its streams in another order, read 0.84.
     static const bool on_side = !(getenv("UAD_AR_STREAM") && !strcmp(getenv("UAD_AR_STREAM"), "own"));
-    if (on_side) { m->ar_stream = m->side; m->ar_own_stream = false; }
-    else if (!m->ar_own_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&m->ar_stream, hipStreamNonBlocking));
-        m->ar_own_stream = true;
-    }
-    for (int i = 0; i < 4; ++i)
-        if (!m->ar_ev_in[i] && hipEventCreateWithFlags(&m->ar_ev_in[i], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess)
-            HIP_TRY(hipEventCreateWithFlags(&m->ar_ev_in[i], hipEventDisableTiming));
-    if (!m->ar_ev_out && hipEventCreateWithFlags(&m->ar_ev_out, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess)
-        HIP_TRY(hipEventCreateWithFlags(&m->ar_ev_out, hipEventDisableTiming));
+    if (const int rc = uad_ar_open(&m->ar, comm, world, m->grads, on_side ? UAD_AR_BORROW : UAD_AR_OWN, m->side)) return rc;
+    for (int i = 0; i < nbuckets; ++i) { m->ar_after[i] = after_segment[i]; m->ar.off[i] = offset[i]; m->ar.cnt[i] = count[i]; }
+    m->ar.nb = nbuckets;
+    return UAD_OK;
+}
+
+// the caller's stream is ordered behind every collective issued so far: on the side stream a join of that stream does it (nothing to add when the segment
+// just run ended with one)
+static int join_allreduce(uad_model* m, hipStream_t st) {
+    if (m->ar.stream != m->side) return uad_ar_join(&m->ar, st);
+    if (m->ar.pending && !m->joined) join_side(m, st);
+    m->ar.pending = false;
     return UAD_OK;
 }
 
 int uad_backward_allreduce(uad_model_t* m, int segment, void* stream) {
     if (!m) return fail(UAD_ERR_INVALID, "null model");
-    if (!m->ar_comm) return fail(UAD_ERR_INVALID, "uad_backward_allreduce without uad_allreduce_attach");
+    if (!m->ar.comm) return fail(UAD_ERR_INVALID, "uad_backward_allreduce without uad_allreduce_attach");
     if (segment == UAD_SEG_ALL || segment == UAD_SEG_ENCODER) return fail(UAD_ERR_INVALID, "uad_backward_allreduce runs ONE of DECODER, BOTTLENECK, ENCODER_HI, ENCODER_LO per call, in that order");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = backward_impl(m, segment, stream, true);
-    if (rc != UAD_OK) return rc;
-    RCCL_API(api);
-    static const bool skip = getenv("UAD_AR_SKIP") != nullptr;       // measurement: everything but the ncclAllReduce call itself
-    for (int i = 0; i < m->ar_nb; ++i) {
-        if (m->ar_after[i] != segment || m->ar_cnt[i] == 0) continue;
-        float* g = m->grads + m->ar_off[i];
+    if (const int rc = backward_impl(m, segment, stream, true)) return rc;
+    for (int i = 0; i < m->ar.nb; ++i) {
+        if (m->ar_after[i] != segment || m->ar.cnt[i] == 0) continue;
         if (m->joined) {
             // The segment ended with the side stream joined into the caller's (the last one always does): its gradients are complete in the
             // CALLER's stream order and the next thing on that stream is the optimizer step, which needs the reduced values anyway -- the
-            // collective goes straight onto the caller's stream, no event and no round trip through another stream.
-            if (m->ar_pending && m->ar_stream != m->side) {
-                // earlier buckets run on the collective stream: the caller's stream waits for them once (the side-stream variant needs nothing: the
-                // segment's own join already ordered the caller's stream behind everything the side stream had been given, collectives included)
-                (void)hipEventRecord(m->ar_ev_out, m->ar_stream);
-                (void)hipStreamWaitEvent(st, m->ar_ev_out, 0);
-            }
-            m->ar_pending = false;
-            if (!skip) RCCL_TRY(api, api->allReduce(g, g, (size_t)m->ar_cnt[i], ncclFloat, ncclSum, (ncclComm_t)m->ar_comm, st));
+            // collective goes straight onto the caller's stream, no event and no round trip through another stream.  Earlier buckets on a stream of
+            // their own are waited for once; the side-stream variant needs nothing: the segment's own join already ordered the caller's stream behind
+            // everything the side stream had been given, collectives included.
+            if (const int rc = join_allreduce(m, st)) return rc;
+            if (const int rc = uad_ar_reduce(&m->ar, i, st)) return rc;
             continue;
         }
         // gradients complete in the SIDE stream's order (deferred segment): one event orders the collective stream behind the slab reductions of
-        // this bucket; the caller's stream is not touched and runs on with the next segment
-        if (m->ar_stream != m->side) {
-            (void)hipEventRecord(m->ar_ev_in[i], m->side);
-            (void)hipStreamWaitEvent(m->ar_stream, m->ar_ev_in[i], 0);
-        }
-        if (!skip) RCCL_TRY(api, api->allReduce(g, g, (size_t)m->ar_cnt[i], ncclFloat, ncclSum, (ncclComm_t)m->ar_comm, m->ar_stream));
-        m->ar_pending = true;
+        // this bucket (none on the side stream itself); the caller's stream is not touched and runs on with the next segment
+        if (const int rc = uad_ar_issue(&m->ar, i, m->side)) return rc;
     }
-    if (segment == UAD_SEG_ENCODER_LO && m->ar_pending) {
-        // (a plan without a bucket behind the last segment: the caller's stream still has to see the earlier ones before the optimizer step)
-        if (m->ar_stream != m->side) {
-            (void)hipEventRecord(m->ar_ev_out, m->ar_stream);
-            (void)hipStreamWaitEvent(st, m->ar_ev_out, 0);
-        } else if (!m->joined) join_side(m, st);
-        m->ar_pending = false;
-    }
+    // (a plan without a bucket behind the last segment: the caller's stream still has to see the earlier ones before the optimizer step)
+    if (segment == UAD_SEG_ENCODER_LO)
+        if (const int rc = join_allreduce(m, st)) return rc;
     HIP_TRY(hipGetLastError());
     return UAD_OK;
 }

@@ -129,7 +129,55 @@ def bucket_plan(segs, buckets):
     return [(after,) + span(parts) for after, parts in groups]
 
 
-class DataParallelStep:
+class _DataParallel:
+    """What DataParallelStep and GanDataParallel share: the choice between the library-issued all-reduce and torch.distributed, the lifetime of the
+    communicator, and the parameter / scalar collectives.  Subclasses set eng, world, comm = None, _own_comm = False, define _attach(comm) (None
+    detaches) and _spans_ranks (whether this rank takes part in collectives)."""
+
+    def _library_allreduce(self, explicit, comm=None):
+        """Attaches the library-issued all-reduce over `comm` (a communicator the caller created earlier) or one of this object's own.  Whether the
+        library path is taken is a COLLECTIVE decision: RcclComm() raises on all ranks or on none, and the attach -- which can fail on one
+        rank alone -- is agreed on before anybody uses it: a rank on the torch process group beside ranks issuing ncclAllReduce on the library's
+        communicator would deadlock the first step.  Otherwise every rank falls back to torch.distributed, or raises if `explicit`."""
+        err = None
+        try:
+            self.comm = comm if comm is not None else RcclComm()
+            self._own_comm = comm is None
+            self._attach(self.comm)
+        except Exception as e:      # librccl not loadable, communicator creation refused (on every rank: RcclComm agrees first), attach refused ...
+            err = e
+        if not _all_ok(err is None):
+            self.close()
+            if explicit:    # asked for explicitly: do not hide the failure (raised on every rank)
+                raise RuntimeError(f'library-issued all-reduce unavailable: {err if err else "another rank failed"}')
+            import sys
+            print(f'uad: library-issued all-reduce unavailable ({err if err else "another rank failed"}); every rank falls back to torch.distributed', file=sys.stderr)
+
+    def close(self):
+        """Detaches the library-issued all-reduce from the engine and destroys the communicator this object created (one per object: re-creating it on
+        the same engine without close() leaked one communicator each time)."""
+        if self.comm is None:
+            return
+        try:
+            if getattr(self.eng, 'handle', None):
+                self._attach(None)
+        finally:
+            if self._own_comm:
+                self.comm.close()
+            self.comm = None
+
+    def broadcast_params(self, src=0):
+        if self._spans_ranks:
+            dist.broadcast(self.eng.buffer(_lib.BUF_PARAMS), src=src)
+
+    def allreduce_scalars(self, scalars):
+        if self._spans_ranks:
+            dist.all_reduce(scalars, op=dist.ReduceOp.SUM)
+            scalars /= self.world
+        return scalars
+
+
+class DataParallelStep(_DataParallel):
     """train_step() for rank-local shards; equal per-rank batch sizes are assumed (weak scaling).
     buckets (default: env UAD_DP_BUCKETS, else 4): how the four gradient segments are merged into all-reduce calls (bucket_plan).
     no_allreduce (default: env UAD_DP_NO_ALLREDUCE): skip the collectives -- the step then trains on the local gradient; bench.py uses the
@@ -162,54 +210,21 @@ class DataParallelStep:
         self.comm = None
         self._own_comm = False
         if want_lib and (self.world > 1 or self.force) and hasattr(engine, 'allreduce_attach'):
-            # Whether the library path is taken is a COLLECTIVE decision: RcclComm() raises on all ranks or on none, and the attach
-            # -- which can fail on one rank alone -- is agreed on before anybody uses it: a rank on the torch process group beside ranks issuing
-            # ncclAllReduce on the library's communicator would deadlock the first train_step.
-            err = None
-            try:
-                self.comm = comm if comm is not None else RcclComm()      # (comm=: a communicator the caller created earlier)
-                self._own_comm = comm is None
-            except Exception as e:      # librccl not loadable, communicator creation refused ...: on every rank (RcclComm agrees before it raises)
-                err = e
-            if err is None:
-                try:
-                    engine.allreduce_attach(self.comm, self.world, self.plan)
-                except Exception as e:
-                    err = e
-            if not _all_ok(err is None):
-                self._drop_comm()
-                if library_allreduce:   # asked for explicitly: do not hide the failure (raised on every rank)
-                    raise RuntimeError(f'library-issued all-reduce unavailable: {err if err else "another rank failed"}')
-                import sys
-                print(f'uad: library-issued all-reduce unavailable ({err if err else "another rank failed"}); every rank falls back to torch.distributed', file=sys.stderr)
+            self._library_allreduce(library_allreduce, comm)
         if self.comm is None and hasattr(engine, 'allreduce_attach') and getattr(engine, '_ar_comm', None) is not None:
             engine.allreduce_attach(None, 1, None)      # a communicator an earlier DataParallelStep left attached must not outlive the choice of the torch path
-            engine._ar_comm = None
         if self.comm is None and (self.world > 1 or self.force) and dist.is_initialized() and dist.get_backend() == 'nccl' and getattr(engine, 'created_before_process_group', False):
             # torch path under RCCL: with the handle created BEFORE the communicator the process group's stream lands on a hardware queue it shares
             # with a stream it waits for -- every all-reduce then costs ~0.2 ms of stall (measured).  Enforced, not only documented.
             raise RuntimeError('DataParallelStep over torch.distributed/nccl: create the process group (init_process_group(..., device_id=...)) BEFORE the '
                                'engine, or use the library-issued all-reduce (UAD_DP_LIBRARY_AR=1, the default)')
 
-    def _drop_comm(self):
-        if self.comm is not None:
-            try:
-                if getattr(self.eng, 'handle', None) and hasattr(self.eng, 'allreduce_attach'):
-                    self.eng.allreduce_attach(None, 1, None)
-                    self.eng._ar_comm = None
-            finally:
-                if self._own_comm:
-                    self.comm.close()
-                self.comm = None
+    @property
+    def _spans_ranks(self):
+        return self.world > 1 or self.force
 
-    def close(self):
-        """Detaches the library-issued all-reduce from the engine and destroys the communicator this object created (one per DataParallelStep: re-creating
-        the step on the same engine without close() leaked one communicator each time)."""
-        self._drop_comm()
-
-    def broadcast_params(self, src=0):
-        if self.world > 1 or self.force:
-            dist.broadcast(self.eng.buffer(_lib.BUF_PARAMS), src=src)
+    def _attach(self, comm):
+        self.eng.allreduce_attach(comm, self.world, self.plan)
 
     def train_step(self, x, eps=None, masks=None, lr=1e-4, beta1=0.5, beta2=0.999, adam_eps=1e-8, **kw):
         eng = self.eng
@@ -242,14 +257,8 @@ class DataParallelStep:
         eng.adam_step(lr, beta1, beta2, adam_eps, 1.0 / self.world)
         return out
 
-    def allreduce_scalars(self, scalars):
-        if self.world > 1 or self.force:
-            dist.all_reduce(scalars, op=dist.ReduceOp.SUM)
-            scalars /= self.world
-        return scalars
 
-
-class GanDataParallel:
+class GanDataParallel(_DataParallel):
     """f-AnoGAN phases under slice-batch DP: every phase loss is a mean over the local batch of per-sample terms (the critic's
     LayerNorm is per sample, the penalty per sample and column), so the all-reduced sum / world of the trained group's gradient
     slice equals the big-batch gradient.  One all-reduce per phase, over that group's slice only (Encoder 1.2 M, Generator
@@ -259,73 +268,41 @@ class GanDataParallel:
         """comm: a communicator the caller created (tests: a stand-in librccl); force_collectives: take the collective path at world 1 too."""
         self.eng = engine
         self.world = world if world is not None else (dist.get_world_size() if dist.is_initialized() else 1)
-        self.grads = engine.buffer(_lib.BUF_GRADS) if self.world > 1 else None
+        self.force = bool(force_collectives)
+        self.grads = engine.buffer(_lib.BUF_GRADS) if (self.world > 1 or self.force) else None
         # library-issued RCCL (round 5): the group's slice is all-reduced ON THE PHASE'S STREAM by libuad_hip.so's own communicator -- stream-ordered
         # between the phase's last gradient kernel and the group's Adam launch, the host does not block and no process-group stream is involved.
         # (The phases of a WGAN iteration form a dependency chain -- every forward reads the parameters the previous phase's Adam wrote -- so there is
         # no later work the collective could legally overlap with; what the library path removes is the blocking host wait and the event hand-off.)
         want_lib = _library_allreduce_default() if library_allreduce is None else bool(library_allreduce)
-        self.comm = comm
-        self._own_comm = False
-        self.in_phase = False          # True: uad_gan_phase all-reduces the trained group itself, in buckets overlapped with its backward (round 6)
-        self.force = bool(force_collectives)
-        if self.force and self.grads is None:
-            self.grads = engine.buffer(_lib.BUF_GRADS)
-        if want_lib and (self.world > 1 or self.force):
-            err = None
-            try:
-                if self.comm is None:
-                    self.comm = RcclComm()      # raises on every rank or on none (it agrees over the group first)
-                    self._own_comm = True
-            except Exception as e:
-                err = e
-            if err is None and hasattr(engine, 'allreduce_attach') and getattr(engine, 'variant', '') != 'aae':
-                try:
-                    engine.allreduce_attach(self.comm, self.world)
-                    self.in_phase = True
-                except Exception as e:
-                    err = e
-            if not _all_ok(err is None):        # (the attach can fail on one rank alone: agree before anybody relies on it)
-                if self.in_phase:
-                    engine.allreduce_attach(None, 1)
-                self.in_phase = False
-                if self._own_comm and self.comm is not None:
-                    self.comm.close()
-                self.comm = None
-                if library_allreduce:
-                    raise RuntimeError(f'library-issued all-reduce unavailable: {err if err else "another rank failed"}')
-                import sys
-                print(f'uad: library-issued all-reduce unavailable ({err if err else "another rank failed"}); every rank falls back to torch.distributed', file=sys.stderr)
-
-    def close(self):
-        if self.in_phase and getattr(self.eng, 'handle', None):
-            self.eng.allreduce_attach(None, 1)
-        self.in_phase = False
-        if self.comm is not None and self._own_comm:
-            self.comm.close()
         self.comm = None
+        self._own_comm = False
+        # (the AAE-family graphs have no bucket hooks: their trainers all-reduce the slice over torch.distributed, step_group)
+        if want_lib and (self.world > 1 or self.force) and getattr(engine, 'variant', '') != 'aae':
+            self._library_allreduce(library_allreduce, comm)
 
-    def broadcast_params(self, src=0):
-        if self.world > 1 and dist.is_initialized():
-            dist.broadcast(self.eng.buffer(_lib.BUF_PARAMS), src=src)
+    @property
+    def in_phase(self):
+        """True: uad_gan_phase all-reduces the trained group itself, in buckets overlapped with its backward (round 6)."""
+        return self.comm is not None
+
+    @property
+    def _spans_ranks(self):
+        return self.world > 1 and dist.is_initialized()
+
+    def _attach(self, comm):
+        self.eng.allreduce_attach(comm, self.world)
 
     def train_phase(self, group, lr, beta1=0.5, beta2=0.9, adam_eps=1e-8, **kw):
         out = self.eng.phase(group, want_backward=True, **kw)
-        if self.in_phase:
-            pass          # the library enqueued the group's bucketed all-reduce behind (and beside) the phase's own backward kernels
-        elif self.world > 1 or self.force:
-            # AnoVAE-GAN's 'Encoder' phase is optim_vae: Encoder + Generator variables (one contiguous slice)
-            red = 'VAE' if (getattr(self.eng, 'variant', '') == 'anovaegan' and group == 'Encoder') else group
-            off, cnt = self.eng.group(red)
-            if self.comm is not None:
-                self.comm.allreduce_(self.grads[off:off + cnt])
-            else:
-                dist.all_reduce(self.grads[off:off + cnt], op=dist.ReduceOp.SUM)
-        self.eng.adam(group, lr, beta1, beta2, adam_eps, 1.0 / self.world)
+        self.step_group(group, lr, beta1, beta2, adam_eps)
         return out
 
-    def allreduce_scalars(self, scalars):
-        if self.world > 1:
-            dist.all_reduce(scalars, op=dist.ReduceOp.SUM)
-            scalars /= self.world
-        return scalars
+    def step_group(self, group, lr, beta1, beta2, adam_eps=1e-8):
+        """After a phase that trained `group`: all-reduces the group's gradient slice over torch.distributed (unless the library already did it inside the
+        phase), then applies the group's Adam with grad_scale = 1 / world.  AnoVAE-GAN's 'Encoder' phase is optim_vae: Encoder + Generator variables (one
+        contiguous slice)."""
+        if not self.in_phase and (self.world > 1 or self.force):
+            off, cnt = self.eng.group('VAE' if (getattr(self.eng, 'variant', '') == 'anovaegan' and group == 'Encoder') else group)
+            dist.all_reduce(self.grads[off:off + cnt], op=dist.ReduceOp.SUM)
+        self.eng.adam(group, lr, beta1, beta2, adam_eps, 1.0 / self.world)

@@ -79,6 +79,11 @@ class AEMODEL(DLMODEL):
     def _make_dp(self, world):
         return DataParallelStep(self.engine, world)
 
+    def close(self):
+        """Tear-down: the data-parallel helper detaches and destroys the communicator it created, then the engine handle goes."""
+        self.dp.close()
+        self.engine.close()
+
     def initialize_variables(self):
         """tf.global_variables_initializer(): glorot_uniform kernels, zero bias, gamma 1, beta 0 (SURVEY §8a note 3)."""
         flat = np.zeros(self.engine.nparams, np.float32)

@@ -50,13 +50,9 @@ class _LatentAE(AEMODEL):
 
     def _phase(self, which, lr, **kw):
         """GanDataParallel.train_phase for the AAE family (all-reduce of the phase's gradient slice, then its Adam)."""
-        import torch.distributed as dist
         out = self.engine.aae_phase(which, want_backward=True, **kw)
-        if self.dp.world > 1:
-            off, cnt = self.engine.group(which)
-            dist.all_reduce(self.dp.grads[off:off + cnt], op=dist.ReduceOp.SUM)
         b1, b2 = (self.config.beta1, 0.999) if self.KIND == 'constrained_ae' else (0.5, 0.9)     # create_optimizer vs the explicit Adams
-        self.engine.adam(which, lr, b1, b2, 1e-8, 1.0 / self.dp.world)
+        self.dp.step_group(which, lr, b1, b2)
         return out
 
     # ------------------------------------------------------------------ one sess.run of the autoencoder fetches

@@ -50,7 +50,6 @@ class GMVAE(GMVAE_spatial):
 
     # ------------------------------------------------------------------ one sess.run of process() (GMVAE.py:116-139)
     def step(self, batch, phase, *, eps=None, fetch_maps=True, masks=None):
-        import torch.distributed as dist
         phase = Phase(phase) if not isinstance(phase, Phase) else phase
         train = phase == Phase.TRAIN
         e_w, e_z = self._draw(len(batch)) if eps is None else eps
@@ -59,10 +58,7 @@ class GMVAE(GMVAE_spatial):
         c = self.config
         out = self.engine.gm_phase(batch, e_w, e_z, masks, want_backward=train, want_l1=fetch_maps)
         if train:
-            if self.dp.world > 1:
-                off, cnt = self.engine.group('AE')
-                dist.all_reduce(self.dp.grads[off:off + cnt], op=dist.ReduceOp.SUM)
-            self.engine.adam('AE', c.learningrate, c.beta1, 0.999, 1e-8, 1.0 / self.dp.world)
+            self.dp.step_group('AE', c.learningrate, c.beta1, 0.999)
         sc = self.dp.allreduce_scalars(torch.stack([out[k] for k in self.SCALAR_KEYS])).cpu().numpy()
         run = {k: np.float32(v) for k, v in zip(self.SCALAR_KEYS, sc)}
         if fetch_maps:
