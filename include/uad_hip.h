@@ -19,6 +19,8 @@
  *   uad_residual
  *       <- utils/Evaluation.py:282-289 (residual map, brain mask, hyper-intensity prior) and
  *          trainers/VAE.py:120 (l1err)
+ *   uad_cc_label / uad_detection_rate / uad_scores_threshold_at_precision
+ *       <- utils/Evaluation.py:130-172 (skimage label + regionprops: lesion-wise TP / FP / FN), :439 (threshold at 70 % precision)
  *   uad_erode_cross / uad_median3d / uad_scores_*
  *       <- utils/Evaluation.py:84-89 (scipy binary_erosion), :108-110 (scipy median_filter), trainers/Metrics.py:17-19,45-47,
  *          67-72,138-162 (sklearn AUPRC / AUROC, Dice threshold sweep)
@@ -258,6 +260,22 @@ int uad_scores_create(const float* pred, const float* label, long long n, uad_sc
 int uad_scores_auc(const uad_scores_t* s, double* auroc, double* auprc, double* positives);
 int uad_scores_dice(uad_scores_t* s, const double* thresholds_host, int k, double* dice_host, void* stream);
 int uad_scores_destroy(uad_scores_t* s);
+/* trainers/Metrics.py:17-19 + utils/Evaluation.py:439 (`np.argmax(_precisions <= 0.7)` on sklearn's precision_recall_curve): the threshold at
+ * the first point of that curve's ordering (increasing threshold) whose precision is <= `precision`; the smallest threshold when no point
+ * qualifies (argmax of all-False is 0).  The result is one of the sorted fp32 scores.  Synchronous, on the stream uad_scores_create ran on. */
+int uad_scores_threshold_at_precision(const uad_scores_t* s, double precision, double* threshold);
+/* 26-connected component labelling of a binary [D,H,W] volume (non-zero = foreground), the device form of skimage.measure.label(volume) as
+ * utils/Evaluation.py:113-127,130-172 call it.  labels [D,H,W] int32 (device): 0 = background, otherwise 1 + the smallest linear index
+ * (z*H + y)*W + x of the voxel's component -- unique, and the component's first voxel in raster order (regionprops' coords[0]).
+ * slab: groups of `slab` consecutive slices are labelled independently (<= 0 or >= D: the whole volume); the reference labels in chunks of 20.
+ * *n_components (device, or NULL) = number of distinct labels.  Union-find: tiles in LDS, tile borders by atomicMin, one flattening pass;
+ * asynchronous, no workspace.  D*H*W < 2^31. */
+int uad_cc_label(const float* vol, int D, int H, int W, int slab, int* labels, int* n_components, void* stream);
+/* utils/Evaluation.py:130-172 compute_detection_rate: per slab, TPs = components of pred & gt; a predicted component of at least min_voxels
+ * (reference: 8) voxels that contains the first voxel of no intersection component is a FP; a ground-truth component that contains none is a
+ * FN.  counts3 (device, 3 x long long) = { TPs, FPs, FNs } summed over the slabs (reference: slab = 20).  The workspace (16 bytes per voxel)
+ * is allocated and freed inside the call, which is therefore synchronous. */
+int uad_detection_rate(const float* pred, const float* gt, int D, int H, int W, int slab, int min_voxels, long long* counts3, void* stream);
 
 /* ---- noise of one step, drawn on the device --------------------------------------------------------------------
  * The reference draws eps (tf.random_normal, models/variational_autoencoder.py:34) and the dropout masks (keras Dropout(rate)(x, training),

@@ -120,6 +120,9 @@ SYMBOLS = {
     'uad_scores_auc': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'uad_scores_dice': (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_void_p]),
     'uad_scores_destroy': (C.c_int, [C.c_void_p]),
+    'uad_scores_threshold_at_precision': (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
+    'uad_cc_label': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_detection_rate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'uad_rng_fill': (C.c_int, [C.POINTER(UadRngJob), C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_void_p]),
     'uad_clock_probe': (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_void_p]),
     'uad_gan_create': (C.c_int, [C.POINTER(UadGanConfig), C.POINTER(C.c_void_p)]),

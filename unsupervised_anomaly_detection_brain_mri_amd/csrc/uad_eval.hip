@@ -318,6 +318,24 @@ __global__ void dice_at_kernel(const float* __restrict__ score, const unsigned l
     out[q] = (2.0 * tps) / (cnt + P);            // 0/0 -> nan like the reference's numpy division
 }
 
+// threshold_at_precision: over the distinct-score positions i (last element of a run of equal scores, descending order) the LARGEST i whose
+// precision tp[i] / (i + 1) is <= p, i.e. the smallest such threshold = the first such point in sklearn's increasing-threshold ordering.
+// best = i + 1 (0: no point qualifies); n < 2^31, so 32 bits hold it.  atomicMax of integers: the result does not depend on the order.
+__global__ void __launch_bounds__(256) prec_threshold_kernel(const float* __restrict__ score, const unsigned long long* __restrict__ tp,
+                                                             unsigned long long n, double p, unsigned* __restrict__ best) {
+    __shared__ unsigned s_best;
+    if (threadIdx.x == 0) s_best = 0;
+    __syncthreads();
+    unsigned mine = 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const bool last = (i + 1 == n) || (score[i] != score[i + 1]);
+        if (last && (double)tp[i] / (double)(i + 1) <= p) mine = (unsigned)(i + 1);        // i grows along the loop
+    }
+    if (mine) atomicMax(&s_best, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_best) atomicMax(best, s_best);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Small-component filter (utils/Evaluation.py:113-127: label(volume, connectivity=3) + regionprops, components with
 // filled_area <= 7 are zeroed).  No labelling pass is needed for that rule: a 26-connected component of at most `maxv` voxels is
@@ -393,6 +411,7 @@ struct uad_scores {
     double* dthr;               // device scratch for threshold batches
     double* dout;
     int cap;
+    hipStream_t stream;         // the stream of uad_scores_create: calls without a stream argument run there
 };
 
 extern "C" {
@@ -442,6 +461,7 @@ int uad_scores_create(const float* pred, const float* label, long long n, uad_sc
     uad_scores* s = new uad_scores();
     memset(s, 0, sizeof *s);
     s->n = (unsigned long long)n;
+    s->stream = st;
     unsigned *key_a = nullptr, *key_b = nullptr, *counts = nullptr, *pos = nullptr, *didx = nullptr, *d_nd = nullptr, *bsum32 = nullptr;
     unsigned char *lab_a = nullptr, *lab_b = nullptr, *flag = nullptr;
     unsigned long long* bsum64 = nullptr;
@@ -524,6 +544,26 @@ int uad_scores_dice(uad_scores_t* s, const double* thresholds, int k, double* di
         EV_TRY(hipMemcpyAsync(dice + o, s->dout, c * sizeof(double), hipMemcpyDeviceToHost, st));
         EV_TRY(hipStreamSynchronize(st));
     }
+    return UAD_OK;
+}
+
+int uad_scores_threshold_at_precision(const uad_scores_t* s, double precision, double* threshold) {
+    if (!s || !threshold || !(precision >= 0.0)) return fail(UAD_ERR_INVALID, "scores_threshold_at_precision: bad arguments");
+    hipStream_t st = s->stream;
+    unsigned* d_best = (unsigned*)s->dout;       // (the handle's threshold-batch scratch; a handle is not thread-safe)
+    EV_TRY(hipMemsetAsync(d_best, 0, sizeof(unsigned), st));
+    const unsigned long long nblk = (s->n + 255) / 256;
+    hipLaunchKernelGGL(prec_threshold_kernel, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(256), 0, st, (const float*)s->score,
+                       (const unsigned long long*)s->tp, s->n, precision, d_best);
+    EV_TRY(hipGetLastError());
+    unsigned best = 0;
+    EV_TRY(hipMemcpyAsync(&best, d_best, sizeof best, hipMemcpyDeviceToHost, st));
+    EV_TRY(hipStreamSynchronize(st));
+    // no point qualifies: numpy's argmax of an all-False array is 0, the smallest threshold
+    float v = 0.f;
+    EV_TRY(hipMemcpyAsync(&v, s->score + (best ? best - 1 : s->n - 1), sizeof v, hipMemcpyDeviceToHost, st));
+    EV_TRY(hipStreamSynchronize(st));
+    *threshold = (double)v;
     return UAD_OK;
 }
 

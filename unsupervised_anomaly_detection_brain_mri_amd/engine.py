@@ -116,6 +116,35 @@ class _EvalOps:
         _lib.check(self.lib.uad_cc_filter(_ptr(v), v.shape[0], v.shape[1], v.shape[2], int(max_voxels), _ptr(out), self._stream()))
         return out
 
+    def _binary_volume(self, volume, what):
+        v = volume if isinstance(volume, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(volume))
+        v = v.to(self.device, torch.float32).contiguous()
+        if v.dim() != 3:
+            raise ValueError(f'{what} expects a [D,H,W] volume')
+        return v
+
+    def cc_label(self, volume, slab=0):
+        """26-connected component labelling of a [D,H,W] volume (bool / float, non-zero = foreground) -> int32 device tensor: 0 = background,
+        otherwise 1 + the smallest linear index of the voxel's component.  slab > 0: groups of `slab` slices are labelled independently
+        (the reference's chunks of 20, utils/Evaluation.py:141)."""
+        v = self._binary_volume(volume, 'cc_label')
+        out = torch.empty(v.shape, device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.uad_cc_label(_ptr(v), v.shape[0], v.shape[1], v.shape[2], int(slab), _ptr(out), None, self._stream()))
+        return out
+
+    def detection_rate(self, pred, gt, slab=20, min_voxels=8):
+        """compute_detection_rate (utils/Evaluation.py:130-172) on the device: lesion-wise (TPs, FPs, FNs) of a predicted against a
+        ground-truth [D,H,W] volume, counted on 26-connected components in chunks of `slab` slices.  Python ints."""
+        p = self._binary_volume(pred, 'detection_rate')
+        g = self._binary_volume(gt, 'detection_rate')
+        if p.shape != g.shape:
+            raise ValueError(f'prediction {tuple(p.shape)} and ground truth {tuple(g.shape)} differ in shape')
+        counts = torch.empty(3, device=self.device, dtype=torch.int64)
+        _lib.check(self.lib.uad_detection_rate(_ptr(p), _ptr(g), p.shape[0], p.shape[1], p.shape[2], int(slab), int(min_voxels), _ptr(counts),
+                                               self._stream()))
+        tps, fps, fns = (int(c) for c in counts.cpu().tolist())
+        return tps, fps, fns
+
     def scores(self, predictions, labels):
         """One descending device sort of all voxel scores -> Scores object (AUROC, AUPRC, dice at thresholds)."""
         return Scores(self, predictions, labels)
@@ -509,6 +538,13 @@ class Scores:
         _lib.check(self.lib.uad_scores_dice(self.handle, t.ctypes.data_as(C.POINTER(C.c_double)), t.size,
                                             out.ctypes.data_as(C.POINTER(C.c_double)), self._stream()))
         return out
+
+    def threshold_at_precision(self, precision):
+        """The threshold of the first point of Metrics.compute_prc's curve (increasing threshold) whose precision is <= `precision`:
+        thr[np.argmax(prec <= precision)] (utils/Evaluation.py:439)."""
+        t = C.c_double()
+        _lib.check(self.lib.uad_scores_threshold_at_precision(self.handle, float(precision), C.byref(t)))
+        return t.value
 
     def close(self):
         if getattr(self, 'handle', None):

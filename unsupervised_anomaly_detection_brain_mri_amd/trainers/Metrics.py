@@ -116,6 +116,21 @@ def recall(P, G):
     return tp / (tp + fn)
 
 
+def tpr(P, G):                                                             # Metrics.py:83-86
+    tp, _, _, fn = confusion_matrix(P, G)
+    return tp / (tp + fn)
+
+
+def fpr(P, G):                                                             # Metrics.py:89-92
+    _, fp, tn, _ = confusion_matrix(P, G)
+    return fp / (fp + tn)
+
+
+def vd(P, G):                                                              # Metrics.py:105-107: missed share of the ground-truth volume
+    P, G = P.flatten().astype(bool), G.flatten().astype(bool)
+    return np.sum(np.logical_xor(P & G, G)) / np.sum(G)
+
+
 def combined_predictive_uncertainty(p, sigmas, axis=-1, log_var=False):     # Metrics.py:170-173
     if log_var:
         sigmas = np.exp(sigmas)

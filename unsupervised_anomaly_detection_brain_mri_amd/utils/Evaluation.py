@@ -6,6 +6,8 @@ array-level core `evaluate_arrays` / `evaluate_volume` (PNG / PDF / NIfTI export
 slices of a volume are reconstructed in ONE batched call (the reference runs one sess.run per slice, :246-250), the brain
 masks are eroded (uad_erode_cross), residual map + mask + hyper-intensity prior come from uad_residual, the 5x5x5 median is
 uad_median3d, and AUROC / AUPRC / the Dice threshold sweep read one device sort of all voxels (uad_scores_*).
+The lesion-wise half of the result (:439-500: TPCC / FPCC / FNCC at the 70 %-precision operating point) runs on the device labelling
+(uad_cc_label / uad_detection_rate); compute_detection_rate below is its host statement.
 erode_brainmask / apply_3d_median_filter keep the reference's scipy calls for host-side use.
 
 Multi-GPU (SURVEY.md 8e "Inference / config 5"): when torch.distributed is initialised the per-patient loop is SHARDED BY PATIENT (patient k of
@@ -225,20 +227,66 @@ def evaluate_arrays(volumes, labels, brainmasks, model, options, eps=None, prior
     return ev
 
 
+def _threshold_at_precision(sc, d_all, l_all, precision):
+    """thr[np.argmax(prec <= precision)] of Metrics.compute_prc: read off the device sort (engine.Scores); a scores object without the
+    device op (the host stand-in engines of the CPU tests) gets the host formula."""
+    if hasattr(sc, 'threshold_at_precision'):
+        return float(sc.threshold_at_precision(precision))
+    _, prec, _, th = Metrics.compute_prc(d_all.cpu().numpy(), np.asarray(l_all).astype(bool))
+    return float(th[np.argmax(prec <= precision)])
+
+
+def _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, options):
+    """utils/Evaluation.py:439-500: the lesion-wise half of the result dictionary.  The volume thresholded at 70 % precision is filtered
+    and compared with every patient's label volume on the device (uad_cc_filter, uad_detection_rate); only three counters per patient
+    come back."""
+    eng = model.engine
+    if options.get('threshold', 'bestdice') == 'bestdice':
+        pred70 = eng.cc_filter((stacked > float(thr70)).to(torch.float32), 7)
+    else:
+        pred70 = pred_dev                        # :455 (the reference's filter works in place, so the alias is the filtered prediction)
+    detect = getattr(eng, 'detection_rate', None)
+    if detect is None:                           # host stand-in engine: the host function on downloaded volumes
+        detect = lambda p, g: compute_detection_rate(p.cpu().numpy(), g)
+    ev['TPCC'] = ev['FPCC'] = ev['FNCC'] = 0
+    s0 = 0
+    for d, g in zip(diffs, gts):
+        tps, fps, fns = detect(pred70[s0:s0 + d.shape[0]], g)
+        s0 += d.shape[0]
+        ev['TPCC'] += int(tps); ev['FPCC'] += int(fps); ev['FNCC'] += int(fns)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for key in ('DiceScore', 'Precision', 'Recall'):
+            per_patient = np.array(ev[key + 'PerPatient'], np.float64)
+            ev[key + 'PerPatientMean'] = float(np.mean(per_patient))
+            ev[key + 'PerPatientStd'] = float(np.std(per_patient))
+        gt_all = np.concatenate(gts, axis=0)
+        ev['TP'], ev['FP'], ev['TN'], ev['FN'] = (int(c) for c in Metrics.confusion_matrix(pred, gt_all))
+        ev['TPR'] = float(Metrics.tpr(pred, gt_all))
+        ev['FPR'] = float(Metrics.tpr(pred, gt_all))       # (the reference computes FPR with Metrics.tpr, :490, sic)
+        ev['VD'] = float(Metrics.vd(pred, gt_all))
+    ev['TPRCC'] = ev['TPCC'] / (ev['TPCC'] + ev['FNCC']) if ev['TPCC'] + ev['FNCC'] > 0 else 0.0
+    ev['PrecisionCC'] = ev['TPCC'] / (ev['TPCC'] + ev['FPCC']) if ev['TPCC'] + ev['FPCC'] > 0 else 0.0
+
+
 def _score_diffs(model, diffs, labels, options, variances=None):
-    """The metric tail of utils/Evaluation.py:416-500 on per-patient residual volumes (device tensors [S,H,W]) and label maps."""
+    """The metric tail of utils/Evaluation.py:416-500 on per-patient residual volumes (device tensors [S,H,W]) and label maps: the
+    voxel-wise scalars and, from _lesionwise_keys, TPCC / FPCC / FNCC / TPRCC / PrecisionCC, TP / FP / TN / FN / TPR / FPR / VD and the
+    per-patient means / standard deviations."""
     d_all = torch.cat([d.reshape(-1) for d in diffs])
     l_all = np.concatenate([np.asarray(l).flatten() for l in labels])
     sc = model.engine.scores(d_all, l_all)
     ev = {'diff_AUC': sc.auroc, 'diff_AUPRC': sc.auprc}
     ev['bestDiceScore'], ev['bestThreshold'] = Metrics.compute_dice_curve_recursive_device(sc, granularity=10)
+    # utils/Evaluation.py:439: the second operating point, the first threshold of the PR curve whose precision is <= 0.7
+    thr70 = _threshold_at_precision(sc, d_all, l_all, 0.7)
     sc.close()
     thr = ev['bestThreshold'] if options.get('threshold', 'bestdice') == 'bestdice' else options['threshold']
     ev['thresholdType'] = options.get('threshold', 'bestdice')
     # utils/Evaluation.py:452-470: threshold, drop the <= 7-voxel components of the STACKED patient volume (device flood-fill
     # filter), then the overall and per-patient Dice / precision / recall
     stacked = torch.cat(diffs, dim=0)
-    pred = model.engine.cc_filter((stacked > float(thr)).to(torch.float32), 7).cpu().numpy() > 0
+    pred_dev = model.engine.cc_filter((stacked > float(thr)).to(torch.float32), 7)
+    pred = pred_dev.cpu().numpy() > 0
     gts = [np.asarray(l).reshape(d.shape).astype(bool) for d, l in zip(diffs, labels)]
     ev['DiceScore'] = Metrics.dice(pred, np.concatenate(gts, axis=0))
     ev['DiceScorePerPatient'], ev['PrecisionPerPatient'], ev['RecallPerPatient'] = [], [], []
@@ -251,6 +299,7 @@ def _score_diffs(model, diffs, labels, options, variances=None):
             ev['PrecisionPerPatient'].append(Metrics.precision(sub, g))
             ev['RecallPerPatient'].append(Metrics.recall(sub, g))
     ev['Dice'] = ev['DiceScorePerPatient']
+    _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, options)
     if variances:
         # utils/Evaluation.py:404-408: histogram of the epistemic variances (50 bins, 1e-5 .. their 99.8th percentile)
         ev['epistemic_variance'] = np.concatenate(variances, axis=0)
