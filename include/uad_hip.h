@@ -226,6 +226,18 @@ int uad_get_math_mode(const uad_model_t* m);
  * sign(x_hat - x) / n per pixel; both report count 0 otherwise), "dec_in" = the decoder's pre-BN input, "G0" / "G1" = gradient
  * ping-pong buffers, "fused_final" = flag in *count. */
 int uad_debug_buffer(uad_model_t* m, const char* name, float** ptr, long long* count);
+/* tests: what the handle WOULD launch for one 5x5 block at batch n (1 .. max_batch) in its current math mode; nothing is launched and no state changes.
+ * side 0 = encoder block `layer` (>= 1; block 0 runs the one-channel first-layer kernels: only its 'W' is answered, kernel 3, with the slab floats it needs),
+ * side 1 = decoder block `layer`; kind 'F' | 'D' | 'W' after
+ * the launchers (encoder: F forward, D data gradient; decoder: D forward, F data gradient; W filter gradient).  out[12]:
+ *   F / D: 0 path (0 generic implicit GEMM | 1 spatial | 2 split-K generic), 1 splits, 2 slabs reduced inside the kernel (ticket counters), 3 column-block
+ *          instance (64 | 32), 4 column-partial tiles, 5 bf16x6 three-plane route (1 taken | 0 refused: exact-fp32 fall-back | -1 other math modes),
+ *          (a training step's operand forms are assumed), 6 fused final epilogue (1 | 0; -1 unless the decoder's last D), 7 0, 8 slab-workspace floats needed, 9 ... allocated,
+ *          10 BN column-partial floats a data gradient writes (0 for a forward), 11 ... allocated per slot;
+ *   W:     0 kernel (0 generic | 1 k5 s2 tile kernel | 2 k3 tap-list kernel | 3 first-layer kernel), 1 splits, 2 last split short, 3 32-channel cs blocks per workgroup (k5: 1 | 2),
+ *          4 work units (8 x 8 output tiles; generic: 32-position K steps), 5 bf16x6 three-plane kernel (1 | 0 | -1), 6 -1, 7 units per split,
+ *          8 filter-gradient slab floats needed, 9 ... allocated per slot, 10 0, 11 as above. */
+int uad_debug_plan(uad_model_t* m, int side, int layer, int kind, int n, long long* out);
 
 /* per-launch-group HIP-event profiler (bench.py's roofline leg).  While enabled, every launch group of
  * uad_forward / uad_backward / uad_adam_step is bracketed by hipEventRecord on the caller's stream.

@@ -56,8 +56,8 @@ def test_forward_backward_parity(arch, h, inter, zdim, n, math):
     if n > 16 and math == 'bf16x3':
         # 80 x 64 x 64 ReLU inputs: a few sit within the split-bf16 round-off of the kink and take the other derivative (measured: dense_dec/kernel
         # 1.3e-3 off at n = 64 and 80 alike, seed-independent, with and without the fused gradient kernel, 6e-7 in f32 mode:
-        # tools/debug/n80_bottleneck_grad.py); the flip-aware comparison at these sample counts is tests/test_gpu_scale_parity.py
-        pytest.skip('needs the flip-aware comparison (tests/test_gpu_scale_parity.py); the ragged-chunk logic under test is math-mode independent')
+        # tools/debug/n80_bottleneck_grad.py); the flip-aware comparison of exactly this case is tests/test_gpu_scale_parity.py::test_vae_small_width_ragged_batch
+        pytest.skip('bf16x3 at n = 80 is held flip-aware by tests/test_gpu_scale_parity.py::test_vae_small_width_ragged_batch; the ragged-chunk logic under test is math-mode independent')
     m, p32, x, eps, masks = _setup(arch, h, inter, zdim, n)
     p64 = _f64(p32)
     out, cache = m.forward(p64, x.astype(np.float64), eps.astype(np.float64) if arch == 'VAE' else None, _f64(masks))

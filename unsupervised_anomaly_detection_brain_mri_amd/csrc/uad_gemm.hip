@@ -2784,10 +2784,17 @@ bool x6_route(const UadConvDesc& d, bool f_type, const GemmPlan& p) {
     const int cst = (d.CS % p.nsplit == 0) ? d.CS / p.nsplit : 0;
     return p.sc.BN == 64 ? (cst == 32 || cst == 64 || cst == 128) : (cst == 32 || cst == 64);
 }
-GemmPlan plan_for(const UadConvDesc& d, bool f_type, bool have_pack, size_t ws_floats, int ncounters, int planes16) {
+// inst_ok: the launch's epilogue / activation-on-load form has a three-plane instance (D kind: d_x6_form_ok; every F form has one).  *x6: the route taken.
+GemmPlan plan_for(const UadConvDesc& d, bool f_type, bool have_pack, size_t ws_floats, int ncounters, int planes16, bool inst_ok = true, bool* x6 = nullptr) {
     GemmPlan p = plan_gemm(d, f_type, have_pack, ws_floats, ncounters);
-    if (planes16 == 3 && !x6_route(d, f_type, p)) p = plan_gemm(d, f_type, have_pack, ws_floats, 0);      // the exact-fp32 kernels: no in-kernel slab reduction
+    const bool take = planes16 == 3 && inst_ok && x6_route(d, f_type, p);
+    if (planes16 == 3 && !take) p = plan_gemm(d, f_type, have_pack, ws_floats, 0);      // the exact-fp32 kernels: no in-kernel slab reduction
+    if (x6) *x6 = take;
     return p;
+}
+// the lane = pixel data-gradient kernel's three-plane instance list (conv5_d16s_takes), by epilogue kind and activation on load
+inline bool d_x6_form_ok(const UadEpilogue& ep, bool has_xf) {
+    return ep.kind == UAD_EPI_FINAL ? (ep.fin_dc == nullptr && ep.ealpha >= 0.f && ep.ealpha <= 1.f && has_xf) : ep.kind == UAD_EPI_BWD_ACT ? !has_xf : has_xf;
 }
 }  // namespace
 bool uad_conv_x6_takes(const UadConvDesc& d, bool f_type, size_t ws_floats, int ncounters) { return x6_route(d, f_type, plan_gemm(d, f_type, true, ws_floats, ncounters)); }
@@ -2811,6 +2818,20 @@ bool uad_conv_d_can_fuse_final_f32(const UadConvDesc& d, bool have_pack, size_t 
     return p.path == PATH_SPATIAL && p.nsplit == 1 && p.sc.TH == 8 && p.sc.TW == 16 && p.sc.BN == 32 && p.sc.CK == 32 && d.CB == 32;
 }
 size_t uad_conv_ws_floats(const UadConvDesc& d, bool f_type, bool have_pack) { return plan_gemm(d, f_type, have_pack, (size_t)1 << 40).ws_floats; }
+// tests (uad_debug_plan): what uad_launch_conv_f / _d would run, from the launchers' own decision functions.  out[10]:
+// 0 path (0 generic | 1 spatial | 2 split-K generic), 1 splits, 2 slabs reduced inside the kernel, 3 column-block instance (64 | 32), 4 column-partial tiles,
+// 5 bf16x6 three-plane route (1 taken | 0 refused: exact-fp32 fall-back | -1 not a bf16x6 launch), 6 -1 (the fused final is the caller's decision), 7 0,
+// 8 workspace floats the plan needs, 9 0 (capacity: the caller's)
+void uad_conv_plan_query(const UadConvDesc& d, bool f_type, bool have_pack, size_t ws_floats, int ncounters, int planes16, bool inst_ok, long long* out) {
+    bool x6 = false;
+    const GemmPlan p = plan_for(d, f_type, have_pack, ws_floats, ncounters, planes16, inst_ok, &x6);      // exactly the launchers' call
+    const int CA = f_type ? d.CB : d.CS, Nn = f_type ? d.CS : d.CB;
+    out[0] = p.path; out[1] = p.nsplit; out[2] = p.inkernel ? 1 : 0;
+    out[3] = p.path == PATH_SPATIAL ? p.sc.BN : choose_tile((long)d.N * d.HS * d.WS, Nn, CA, f_type ? 1 : d.S * d.S).BN;
+    out[4] = p.tiles;
+    out[5] = planes16 == 3 ? (x6 ? 1 : 0) : -1;
+    out[6] = -1; out[7] = 0; out[8] = (long long)p.ws_floats; out[9] = 0;
+}
 
 void uad_launch_pack_weights(const float* params, float* wpack_f, float* wpack_d, const long long* offs, const int* cbs,
                              const int* css, const int* taps, int n, hipStream_t st) {
@@ -2928,13 +2949,13 @@ void uad_launch_conv_f(const UadConvDesc& d, const float* big_in, UadXform xf, c
     a.M = d.N * d.HS * d.WS; a.CA = d.CB; a.Nn = d.CS;
     a.lws = ilog2_exact(d.WS); a.lhs = ilog2_exact(d.HS); a.dbgbuf = nullptr;
     a.sk_counter = nullptr; a.out_final = nullptr;
-    GemmPlan p = plan_gemm(d, true, Wpacked != nullptr || Wp16 != nullptr, ws.ptr ? ws.floats : 0, (Wp16 && ws.counters) ? ws.ncounters : 0);
+    bool x6 = false;
+    const GemmPlan p = plan_for(d, true, Wpacked != nullptr || Wp16 != nullptr, ws.ptr ? ws.floats : 0, (Wp16 && ws.counters) ? ws.ncounters : 0, planes16, true, &x6);
     if (planes16 == 3) {
-        if (x6_route(d, true, p)) a.npl = 3;
-        else {      // bf16x6 handle, launch outside the three-plane kernels: the exact-fp32 route
+        if (x6) a.npl = 3;
+        else {      // bf16x6 handle, launch outside the three-plane kernels: the exact-fp32 route (plan_for planned it: needs the fp32 pack wherever a spatial kernel could run)
             if (!Wpacked && d.KS == 5) { fprintf(stderr, "uad: a bf16x6 launch outside the three-plane spatial kernels needs the fp32 pack (uad_conv_x6_takes / uad_conv_k3_takes)\n"); abort(); }
             a.Wp16 = nullptr;
-            p = plan_gemm(d, true, Wpacked != nullptr, ws.ptr ? ws.floats : 0, 0);
         }
     }
     if (p.inkernel) a.sk_counter = ws.counters;
@@ -2951,16 +2972,14 @@ void uad_launch_conv_d(const UadConvDesc& d, const float* small_in, UadXform xf,
     a.M = d.N * d.HS * d.WS; a.CA = d.CS; a.Nn = d.CB;
     a.lws = ilog2_exact(d.WS); a.lhs = ilog2_exact(d.HS); a.dbgbuf = nullptr;
     a.sk_counter = nullptr; a.out_final = nullptr;
-    GemmPlan p = plan_gemm(d, false, Wpacked != nullptr || Wp16 != nullptr, ws.ptr ? ws.floats : 0, (Wp16 && ws.counters) ? ws.ncounters : 0);
+    bool x6 = false;
+    const GemmPlan p = plan_for(d, false, Wpacked != nullptr || Wp16 != nullptr, ws.ptr ? ws.floats : 0, (Wp16 && ws.counters) ? ws.ncounters : 0, planes16,
+                                d_x6_form_ok(ep, xf.scale != nullptr), &x6);
     if (planes16 == 3) {
-        // (the lane = pixel kernel's instance list: conv5_d16s_takes)
-        const bool has_xf = xf.scale != nullptr;
-        const bool inst_ok = ep.kind == UAD_EPI_FINAL ? (ep.fin_dc == nullptr && ep.ealpha >= 0.f && ep.ealpha <= 1.f && has_xf) : ep.kind == UAD_EPI_BWD_ACT ? !has_xf : has_xf;
-        if (x6_route(d, false, p) && inst_ok) a.npl = 3;
+        if (x6) a.npl = 3;
         else {
             if (!Wpacked && d.KS == 5) { fprintf(stderr, "uad: a bf16x6 launch outside the three-plane spatial kernels needs the fp32 pack (uad_conv_x6_takes / uad_conv_k3_takes)\n"); abort(); }
             a.Wp16 = nullptr;
-            p = plan_gemm(d, false, Wpacked != nullptr, ws.ptr ? ws.floats : 0, 0);
         }
     }
     if (p.inkernel) a.sk_counter = ws.counters;
@@ -3010,6 +3029,11 @@ void launch_w_tr_n(const ConvWArgs& a, dim3 grid, const W5Choice& w5, hipStream_
 // bf16x6 instances: the three operand forms the model's backward uses -- (pattern word | plain gradient, activated input) in the decoder, (activated input,
 // plain gradient) in the encoder; w_tr_x6_takes() tells the launcher, other forms of a bf16x6 launch run on the exact-fp32 generic kernels
 inline bool w_tr_x6_takes(bool fbb, bool xa, bool xs) { return fbb ? xs : (xa != xs); }
+// the k5 s2 filter gradient of a launch in a split-bf16 mode runs on the bf16 kernel unless it is a bf16x6 launch of an operand form without a three-plane instance
+inline bool w5_use16(bool math_bf16x3, int planes16, bool fbb, bool xa, bool xs) { return math_bf16x3 && !(planes16 == 3 && !w_tr_x6_takes(fbb, xa, xs)); }
+// 32-channel cs blocks per workgroup of that kernel: two (512 threads) where the layer has them; the exact-fp32 kernel takes one
+inline int w5_ncsb(const UadConvDesc& d, bool use16) { return (use16 && d.CS % 64 == 0) ? 2 : 1; }
+inline bool wk3_takes(const WK3Choice& k3, bool any16, int planes16, bool defer_reduce, bool any_xf) { return k3.ok && any16 && planes16 != 3 && !defer_reduce && !any_xf; }
 template <int NCSB, bool FBB, bool XFA, bool XFS>
 void launch_w_tr(const ConvWArgs& a, dim3 grid, const W5Choice& w5, hipStream_t st) {
     if constexpr (FBB ? XFS : (XFA != XFS)) { if (a.npl == 3) { launch_w_tr_n<NCSB, FBB, XFA, XFS, 3>(a, grid, w5, st); return; } }
@@ -3043,11 +3067,9 @@ void uad_launch_conv_w(const UadConvDesc& d, const float* big, UadXform xfb, con
         return reduce_st;
     };
     const W5Choice w5 = choose_w5(d, math_bf16x3);
-    bool use16 = math_bf16x3;
-    if (w5.ok && math_bf16x3 && planes16 == 3 && !w_tr_x6_takes(xfb.fb_bits != nullptr, xfb.scale != nullptr && !xfb.fb_bits, xfs.scale != nullptr)) {
-        if (xfb.fb_bits) { fprintf(stderr, "uad: bf16x6 filter gradient from the pattern word needs the small operand's activation on load\n"); abort(); }
-        use16 = false;      // the exact-fp32 k5 kernel on the SAME split (uad_launch_conv_w_reduce is told the launch's math mode, not the kernel)
-    }
+    // (a bf16x6 launch outside the three-plane instances: the exact-fp32 k5 kernel on the SAME split -- uad_launch_conv_w_reduce is told the launch's math mode, not the kernel)
+    const bool use16 = w5_use16(math_bf16x3, planes16, xfb.fb_bits != nullptr, xfb.scale != nullptr && !xfb.fb_bits, xfs.scale != nullptr);
+    if (w5.ok && math_bf16x3 && !use16 && xfb.fb_bits) { fprintf(stderr, "uad: bf16x6 filter gradient from the pattern word needs the small operand's activation on load\n"); abort(); }
     if (w5.ok) {
         ConvWArgs a;
         a.big = big; a.small_ = small; a.partial = (w5.splits == 1) ? dW : partial;
@@ -3071,7 +3093,7 @@ void uad_launch_conv_w(const UadConvDesc& d, const float* big, UadXform xfb, con
                 fprintf(stderr, "[w5 CB=%d CS=%d HS=%d grid=%d,%d,%d] span=%llu (100MHz ticks) wg dur min=%llu avg=%llu max=%llu latest start=%llu\n", d.CB, d.CS, d.HS, g->x, g->y, g->z,
                         t1 - t0, dmin, dsum / nb, dmax, smax); } } dump{dbg_this, st, wbuf, &grid, &wcalls, d};
         if (use16) {
-            const bool two = d.CS % 64 == 0;       // two 32-channel cs blocks per workgroup (512 threads) where the layer has them
+            const bool two = w5_ncsb(d, true) == 2;       // two 32-channel cs blocks per workgroup (512 threads) where the layer has them
             if (two) grid.y = d.CS / 64;
             {
                 const bool xa = xfb.scale != nullptr && !xfb.fb_bits, xs = xfs.scale != nullptr;
@@ -3090,7 +3112,7 @@ void uad_launch_conv_w(const UadConvDesc& d, const float* big, UadXform xfb, con
         return;
     }
     const WK3Choice k3 = choose_wk3(d);
-    if (k3.ok && (math_bf16x3 || generic_bf16x3) && planes16 != 3 && !defer_reduce && !xfb.scale && !xfs.scale && !xfb.fb_bits) {
+    if (wk3_takes(k3, math_bf16x3 || generic_bf16x3, planes16, defer_reduce, xfb.scale || xfs.scale || xfb.fb_bits)) {
         // k3 s1 / s2 filter gradient in bf16x3 (uad_convk16.inc): channel-major LDS tiles, slabs + fixed-order reduction
         ConvWArgs a;
         a.big = big; a.small_ = small; a.partial = (k3.splits == 1) ? dW : partial;
@@ -3131,4 +3153,29 @@ void uad_launch_conv_w_reduce(const UadConvDesc& d, float* dW, float* partial, h
     const W5Choice w5 = choose_w5(d, math_bf16x3);
     const int splits = w5.ok ? w5.splits : choose_w(d).splits;
     if (splits > 1) uad_launch_reduce_partials(partial, splits, d.KS * d.KS * d.CB * d.CS, 1.0f, dW, st);
+}
+
+// tests (uad_debug_plan): what uad_launch_conv_w would run.  out[10]: 0 kernel (0 generic | 1 k5 s2 tile kernel, choose_w5 | 2 k3 tap-list kernel), 1 splits,
+// 2 the last split is short, 3 32-channel cs blocks per workgroup (k5: 1 | 2; else 0), 4 work units (k5 / k3: 8 x 8 output tiles; generic: 32-position K steps),
+// 5 bf16x6 three-plane kernel (1 | 0 exact-fp32 kernel | -1 not a bf16x6 launch), 6 -1, 7 units per split, 8 slab floats the launch writes, 9 0 (capacity: the caller's)
+void uad_conv_w_plan_query(const UadConvDesc& d, bool math_bf16x3, int planes16, bool fbb, bool xa, bool xs, bool generic_bf16x3, bool defer_reduce, long long* out) {
+    const long long slab = (long long)d.KS * d.KS * d.CB * d.CS;
+    out[5] = -1; out[6] = -1; out[9] = 0;
+    const W5Choice w5 = choose_w5(d, math_bf16x3);
+    if (w5.ok) {
+        const bool use16 = w5_use16(math_bf16x3, planes16, fbb, xa, xs);
+        out[0] = 1; out[1] = w5.splits; out[2] = (w5.total_tiles % w5.tiles_per_split) ? 1 : 0; out[3] = w5_ncsb(d, use16); out[4] = w5.total_tiles;
+        if (math_bf16x3 && planes16 == 3) out[5] = use16 ? 1 : 0;
+        out[7] = w5.tiles_per_split; out[8] = w5.splits > 1 ? w5.splits * slab : 0;
+        return;
+    }
+    const WK3Choice k3 = choose_wk3(d);
+    if (wk3_takes(k3, math_bf16x3 || generic_bf16x3, planes16, defer_reduce, fbb || xa || xs)) {
+        out[0] = 2; out[1] = k3.splits; out[2] = (k3.total_tiles % k3.tiles_per_split) ? 1 : 0; out[3] = 0; out[4] = k3.total_tiles;
+        out[7] = k3.tiles_per_split; out[8] = k3.splits > 1 ? k3.splits * slab : 0;
+        return;
+    }
+    const WChoice c = choose_w(d);
+    const long long Kt = (long long)d.N * d.HS * d.WS;
+    out[0] = 0; out[1] = c.splits; out[2] = (Kt % c.kper) ? 1 : 0; out[3] = 0; out[4] = (Kt + 31) / 32; out[7] = c.kper / 32; out[8] = c.splits > 1 ? c.splits * slab : 0;
 }

@@ -119,6 +119,9 @@ bool uad_conv_f_supports_final_bwd(const UadConvDesc& d, bool have_pack16, size_
 int uad_conv_d_tiles(const UadConvDesc& d, bool have_pack = true, size_t ws_floats = 0, int ncounters = 0, int planes16 = 2);
 // workspace floats the split-K path would like for this op (0 = it would not split)
 size_t uad_conv_ws_floats(const UadConvDesc& d, bool f_type, bool have_pack);
+// tests (uad_debug_plan): the launch plan of uad_launch_conv_f / _d / _w as ten integers (fields: uad_gemm.hip, include/uad_hip.h)
+void uad_conv_plan_query(const UadConvDesc& d, bool f_type, bool have_pack, size_t ws_floats, int ncounters, int planes16, bool inst_ok, long long* out);      // inst_ok: D kind, the epilogue form has a three-plane instance
+void uad_conv_w_plan_query(const UadConvDesc& d, bool math_bf16x3, int planes16, bool fbb, bool xa, bool xs, bool generic_bf16x3, bool defer_reduce, long long* out);
 // W-type: dW[tap][cb][cs] = sum_{n,i,j} xfb(big)[..tap..,cb] * xfs(small)[n,i,j,cs]
 // `partial` must hold uad_conv_w_partial_floats(d) floats.
 size_t uad_conv_w_partial_floats(const UadConvDesc& d);

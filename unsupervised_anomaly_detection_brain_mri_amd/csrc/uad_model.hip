@@ -478,14 +478,16 @@ int uad_create(const uad_config_t* cfg, uad_model_t** out) {
     m->ev_next = 0; m->side = nullptr;
     if (rc == UAD_OK && hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess) rc = fail(UAD_ERR_HIP, "hipStreamCreate failed");
     size_t wp = 0;
-    auto wp_need = [&](UadConvDesc d) { d.N = (int)NB; size_t v = uad_conv_w_partial_floats(d); if (v > wp) wp = v; };
+    // over EVERY row count the handle may be given, not just max_batch: the split count of the k5 filter gradient is not monotone in the batch (choose_w5:
+    // 17 slices of a 128 x 128 handle give enc1 136 slabs of two tiles, 16 slices 256 slabs of one)
+    auto wp_need = [&](UadConvDesc d) { for (size_t nb = m->nmul; nb <= NB; nb += m->nmul) { d.N = (int)nb; size_t v = uad_conv_w_partial_floats(d); if (v > wp) wp = v; } };
     for (size_t i = 1; i < m->enc.size(); ++i) wp_need(m->enc[i].d);
     for (auto& L : m->dec) wp_need(L.d);
     if (!gm && !sp) {
         wp_need(conv1x1_desc(1, ir, ir, m->cenc, m->cmid)); wp_need(conv1x1_desc(1, ir, ir, m->cmid, m->cenc));
         wp_need(dense_desc(1, m->flat, cfg->zdim)); wp_need(dense_desc(1, cfg->zdim, m->flat));
     }
-    { UadConvDesc d0 = m->enc[0].d; d0.N = (int)NB; size_t v = uad_conv_first_wgrad_partial_floats(d0); if (v > wp) wp = v; }
+    { UadConvDesc d0 = m->enc[0].d; for (size_t nb = m->nmul; nb <= NB; nb += m->nmul) { d0.N = (int)nb; size_t v = uad_conv_first_wgrad_partial_floats(d0); if (v > wp) wp = v; } }      // (rows per block grow with the batch: not monotone either)
     m->wpartial_cap = wp; ALLOC(m->wpartial, wp);
     for (int k = 0; k < 16; ++k) { m->wp_slot[k] = nullptr; ALLOC(m->wp_slot[k], wp); }
     {
@@ -711,6 +713,18 @@ int uad_set_fault_deferred(uad_model_t* m, int on) {
 }
 // (Plane-group tensors -- every producer also writing its ACTIVATED output pre-split into bf16 hi | lo groups for the consumers -- were built and
 // measured in round 3: parity-green, 2 % slower; removed in round 4, tools/experiments/r03_pruned_opt_in_paths.patch.)
+// last decoder block: may its ConvT kernel run the final 1x1 conv + loss in its epilogue? (d.N = the rows of the launch)
+static bool fuse_final_ok(const uad_model* m, const UadConvDesc& d) {
+    const int bps = uad_final_blocks_per_sample(m->cfg.height, m->cfg.width);
+    return (bf_mode(m) ? uad_conv_d_can_fuse_final(d, true, m->ws.floats) : uad_conv_d_can_fuse_final_f32(d, m->math == UAD_MATH_F32, m->ws.floats)) &&
+           (d.HS / 8) * (d.WS / 16) == bps;
+}
+
+// ... and may that epilogue leave d loss / d c as one pattern word + one float per pixel (both consumers expand it on load)?
+static bool fin_bits_ok(const uad_model* m, const UadConvDesc& d, int want_backward) {
+    return bf_mode(m) && d.CB <= 32 && uad_conv_f_supports_final_bwd(d, true, m->ws.floats) && (want_backward == 2 || uad_conv_w_supports_fb_bits(d, true));
+}
+
 int uad_forward(uad_model_t* m, const uad_io_t* io, int n, int want_backward, void* stream) {
     if (!m || !io) return fail(UAD_ERR_INVALID, "null argument");
     if (n <= 0 || n > m->cfg.max_batch) return fail(UAD_ERR_INVALID, "batch %d outside (0, max_batch=%d]", n, m->cfg.max_batch);
@@ -824,8 +838,7 @@ int uad_forward(uad_model_t* m, const uad_io_t* io, int n, int want_backward, vo
         UadEpilogue ep = epi_bias(P(m, m->dec[i].b));
         float* out = m->dec[i].c;
         const bool bfm = bf_mode(m);
-        if (i + 1 == m->dec.size() && (bfm ? uad_conv_d_can_fuse_final(d, true, m->ws.floats) : uad_conv_d_can_fuse_final_f32(d, m->math == UAD_MATH_F32, m->ws.floats)) &&
-            (d.HS / 8) * (d.WS / 16) == bps) {
+        if (i + 1 == m->dec.size() && fuse_final_ok(m, d)) {
             // last block: its BN + LeakyReLU, the final 1x1 conv, the L1 loss and (training) the loss gradient run in the
             // ConvT kernel's epilogue; the pre-BN output is only written when a later pass needs it (restoration: TV term)
             fused_final = true;
@@ -838,8 +851,7 @@ int uad_forward(uad_model_t* m, const uad_io_t* io, int n, int want_backward, vo
             ep.fin_rec_partial = m->rec_partial; ep.fin_red_partial = m->red_partial;
             ep.fin_dc = (want_backward && !restore_bwd) ? m->G0 : nullptr;
             ep.fin_bits = nullptr; ep.fin_dxhat = nullptr;
-            if (bfm && ep.fin_dc && d.CB <= 32 && uad_conv_f_supports_final_bwd(d, true, m->ws.floats) &&
-                (want_backward == 2 || uad_conv_w_supports_fb_bits(d, true))) {
+            if (ep.fin_dc && fin_bits_ok(m, d, want_backward)) {
                 // both consumers of d loss / d c (this layer's data- and filter-gradient kernels) can expand it from one pattern word +
                 // one float per pixel: 8 B instead of 128 B per pixel written here and read twice in the backward
                 ep.fin_dc = nullptr; ep.fin_bits = m->fin_bits; ep.fin_dxhat = m->fin_dxh;
@@ -1436,6 +1448,44 @@ int uad_debug_buffer(uad_model_t* m, const char* name, float** ptr, long long* c
     }
     if (ptr) *ptr = p;
     if (count) *count = c;
+    return UAD_OK;
+}
+
+// tests: the launch plan of one 5x5 block at batch n in the handle's current math mode -- nothing is launched.  side 0 = encoder block `layer` (>= 1: block 0 runs the
+// one-channel first-layer kernels), 1 = decoder block `layer`; kind 'F' / 'D' / 'W' as the launchers are named (encoder: F forward, D data gradient; decoder: D
+// forward, F data gradient; W filter gradient).  Same decision functions, same arguments as uad_forward / uad_backward pass.
+int uad_debug_plan(uad_model_t* m, int side, int layer, int kind, int n, long long* out) {
+    if (!m || !out) return fail(UAD_ERR_INVALID, "null argument");
+    if (n <= 0 || n > m->cfg.max_batch) return fail(UAD_ERR_INVALID, "batch %d outside (0, max_batch=%d]", n, m->cfg.max_batch);
+    if (side == 0 && layer == 0 && kind == 'W') {      // the one-channel first-layer filter gradient: its per-block slabs share the filter-gradient slab buffer
+        UadConvDesc d0 = m->enc[0].d; d0.N = n * m->nmul;
+        for (int k = 0; k < 12; ++k) out[k] = 0;
+        out[0] = 3; out[5] = -1; out[6] = -1; out[8] = (long long)uad_conv_first_wgrad_partial_floats(d0); out[9] = (long long)m->wpartial_cap; out[11] = (long long)m->colpart_cap;
+        out[1] = out[8] / ((long long)d0.KS * d0.KS * d0.CB * d0.CS);
+        return UAD_OK;
+    }
+    if (side < 0 || side > 1 || layer < (side == 0 ? 1 : 0) || layer >= (int)(side == 0 ? m->enc.size() : m->dec.size()))
+        return fail(UAD_ERR_INVALID, "no planned block: side %d layer %d", side, layer);
+    UadConvDesc d = side == 0 ? m->enc[layer].d : m->dec[layer].d;
+    d.N = n * m->nmul;
+    if (kind == 'F' || kind == 'D') {
+        // D kind: every form of a training step has a three-plane instance (encoder data gradient: plain input, activation backward; decoder forward: activation on
+        // load) except a fused final that has to leave d loss / d c uncompressed (uad_launch_conv_d: d_x6_form_ok)
+        const bool last_d = kind == 'D' && side == 1 && layer + 1 == (int)m->dec.size();
+        const bool fused = last_d && fuse_final_ok(m, d);
+        uad_conv_plan_query(d, kind == 'F', true, m->ws.floats, sk_counters(m), planes_of(m), !(fused && !fin_bits_ok(m, d, 1)), out);
+        out[9] = (long long)m->ws.floats;
+        if (last_d) out[6] = fused ? 1 : 0;
+        // the data gradients leave one row of BN column partials per tile in a cp_slot: floats needed (2 per column) and the slot's size
+        const bool dgrad = (side == 0) == (kind == 'D');
+        out[10] = dgrad ? out[4] * 2 * (kind == 'F' ? d.CS : d.CB) : 0;
+        out[11] = (long long)m->colpart_cap;
+    } else if (kind == 'W') {
+        // operand forms of backward_decoder / backward_encoder: (pattern word | plain gradient, activated input) and (activated input, plain gradient); slabs deferred
+        const bool fbb = side == 1 && layer + 1 == (int)m->dec.size() && fuse_final_ok(m, d) && fin_bits_ok(m, d, 1);
+        uad_conv_w_plan_query(d, bf_mode(m), planes_of(m), fbb, side == 0, side == 1, false, true, out);
+        out[9] = (long long)m->wpartial_cap; out[10] = 0; out[11] = (long long)m->colpart_cap;
+    } else return fail(UAD_ERR_INVALID, "kind must be 'F', 'D' or 'W'");
     return UAD_OK;
 }
 
