@@ -36,6 +36,8 @@
 #ifndef UAD_HIP_H
 #define UAD_HIP_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -315,6 +317,25 @@ int uad_clock_probe(unsigned long long* out2, unsigned long long ticks_100mhz, v
 int uad_gather_slices(const float* src, const int* idx, int n, long long slice_elems, float* out, void* stream);
 int uad_gather_mask(const unsigned char* labels, const int* idx, int n, long long slice_px, const unsigned char* lut256, float* out,
                     void* stream);
+
+/* ---- cubic-spline slice resampling (utils/Evaluation.py:223-232, 323-334; the slice ingestion of the dataloaders) ------------
+ * uad_zoom_spline3: scipy.ndimage.zoom(a, (H/h, W/w), order=3, mode=..., prefilter=True, grid_mode=False) of every [h,w] slice of an
+ *   fp32 [n,h,w] batch -> [n,H,W].  The CALLER fixes the output shape (scipy: round(h * zoom)); output sample o reads input coordinate
+ *   o (h-1)/(H-1) (0 when H == 1).  boundary UAD_ZOOM_CONSTANT = scipy mode 'constant' with cval 0: no padding, the prefilter and the
+ *   taps that step over the edge use the mirror extension (c[-1] = c[1]); UAD_ZOOM_NEAREST = scipy mode 'nearest': every line is extended
+ *   by 12 edge-replicated samples on each side, filtered with the mirror recursion, and the taps read the padded coefficients.
+ *   out_kind UAD_ZOOM_F32: fp32 [n,H,W]; UAD_ZOOM_I32: int32 [n,H,W], t > 0 ? (int)(t + 0.5) : (int)(t - 0.5) -- what scipy does to an
+ *   integer-typed input (label / skull maps): the same spline, rounded half away from zero, NOT nearest-neighbour sampling.
+ *   Coefficients (pole sqrt(3) - 2, gain 6 per axis) and interpolation are fp64 so that the integer maps round as scipy rounds them.
+ *   A 3-D zoom of [S,h,w] with factor 1 on axis 0 is this call with n = S (the coefficients of a factor-1 axis evaluated at its
+ *   knots are the samples), so one entry serves ingestion and the exportVolumes de-zoom.  h, w >= 2.  No atomics: a slice's result
+ *   does not depend on n.  workspace: device memory of at least uad_zoom_spline3_workspace(n, h, w, boundary) bytes (the fp64
+ *   coefficient planes), 16-byte aligned, owned by the caller and free for reuse once the call's work on `stream` is done. */
+enum { UAD_ZOOM_CONSTANT = 0, UAD_ZOOM_NEAREST = 1 };
+enum { UAD_ZOOM_F32 = 0, UAD_ZOOM_I32 = 1 };
+size_t uad_zoom_spline3_workspace(int n, int h, int w, int boundary);
+int uad_zoom_spline3(const float* in, int n, int h, int w, int H, int W, int boundary, int out_kind, void* out, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 /* ---- f-AnoGAN (unified graph) ------------------------------------------------------------------------------
  * Replaces models/fanogan.py:11-84 (encoder + generator + critic graph) and the three optimisation phases of

@@ -1,0 +1,207 @@
+"""GPU: the device cubic-spline slice resampler (uad_zoom_spline3 through engine._EvalOps.zoom) and the paths built on it
+(Evaluation.collect_patient_volume(engine=...), options['resampleOnDevice'] / ['exportVolumes'], nifti.volume_to_slices(engine=...)).
+
+The reference is always scipy.ndimage.zoom run in fp64 on the fp32-rounded input, never the code under test.
+  fp32 output: max-abs error <= 1.2e-7 for inputs in [0,1].  fp64 arithmetic leaves about 1e-15; the final fp32 rounding leaves half an ulp,
+      6e-8 for |v| < 2 (spline overshoot keeps |v| < 2); the bar is twice that.
+  int32 output: exact equality with scipy's result for the integer-typed map.  A voxel may be left out only where scipy's unrounded value lies
+      within 1e-9 of a half-integer (at most 1e-5 of the voxels), and the inputs are chosen -- on scipy alone -- to have ZERO such voxels."""
+import glob
+import os
+import types
+
+import numpy as np
+import pytest
+import scipy.ndimage
+import torch
+
+pytestmark = pytest.mark.gpu
+
+try:
+    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine, zoom_output_hw
+    from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation, nifti
+    from unsupervised_anomaly_detection_brain_mri_amd.utils.default_config_setup import get_options
+    from unsupervised_anomaly_detection_brain_mri_amd.utils.synthetic import SyntheticPatientDataset
+except Exception:
+    Engine = None
+
+F32_BAR = 1.2e-7
+TIE_WINDOW = 1e-9
+MODES = ('constant', 'nearest')
+# (h, w, H, W): ingestion, the synthetic patients' ingestion, the two de-zooms, the identity, a non-square factor pair, a 5-sample line
+CASES = [(217, 181, 128, 128), (80, 80, 64, 64), (128, 128, 217, 181), (64, 64, 80, 80), (128, 128, 128, 128), (100, 60, 50, 90), (5, 40, 8, 64)]
+BATCHES = (1, 7)             # n = 1 and a ragged n (not a multiple of any tile or wave size)
+
+
+@pytest.fixture(scope='module')
+def eng():
+    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    yield e
+    e.close()
+
+
+def scipy_zoom(a, H, W, mode):
+    """scipy on one [h,w] slice with the factors that give the (H, W) output (the dtype of `a` decides float / integer behaviour)."""
+    out = scipy.ndimage.zoom(a, (H / a.shape[0], W / a.shape[1]), order=3, mode=mode)
+    assert out.shape == (H, W)
+    return out
+
+
+def near_ties(unrounded):
+    return int(np.count_nonzero(np.abs(np.abs(unrounded - np.floor(unrounded)) - 0.5) < TIE_WINDOW))
+
+
+def float_batch(n, h, w, seed):
+    return np.random.default_rng(seed).random((n, h, w)).astype(np.float32)
+
+
+def integer_batch(n, h, w, H, W, mode, seed):
+    """Blob-shaped integer maps (labels 0..2) without a near-tie voxel under scipy alone: the first of a fixed seed sequence that has none."""
+    for s in range(seed, seed + 200):
+        rng = np.random.default_rng(s)
+        f = scipy.ndimage.gaussian_filter(rng.standard_normal((n, h, w)), (0, min(h, 8) / 4.0, min(w, 8) / 4.0))
+        m = (f > np.quantile(f, 0.55)).astype(int) + (f > np.quantile(f, 0.9)).astype(int)
+        un = np.stack([scipy_zoom(m[k].astype(np.float64), H, W, mode) for k in range(n)])
+        if near_ties(un) == 0:
+            return m, un
+    raise AssertionError('no tie-free integer input found')
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('case', CASES, ids=lambda c: '%dx%d-%dx%d' % c)
+def test_fp32_output_against_scipy_fp64(eng, case, mode):
+    h, w, H, W = case
+    for n in BATCHES:
+        a = float_batch(n, h, w, seed=h + 3 * H + n)
+        ref = np.stack([scipy_zoom(a[k].astype(np.float64), H, W, mode) for k in range(n)])
+        got = eng.zoom(a, (H, W), mode=mode)
+        assert got.dtype == torch.float32 and tuple(got.shape) == (n, H, W)
+        err = float(np.abs(got.cpu().numpy().astype(np.float64) - ref).max())
+        print(f'zoom fp32 {case} {mode} n={n}: max-abs err {err:.3e} (|ref| max {np.abs(ref).max():.3f})')
+        assert np.abs(ref).max() < 2.0
+        assert err <= F32_BAR
+
+
+@pytest.mark.parametrize('mode', MODES)
+@pytest.mark.parametrize('case', CASES, ids=lambda c: '%dx%d-%dx%d' % c)
+def test_int32_output_equals_scipy_on_integer_maps(eng, case, mode):
+    h, w, H, W = case
+    for n in BATCHES:
+        m, unrounded = integer_batch(n, h, w, H, W, mode, seed=1000 + h + n)
+        assert near_ties(unrounded) == 0                       # the condition on the inputs, on scipy alone
+        ref = np.stack([scipy_zoom(m[k], H, W, mode) for k in range(n)])
+        assert np.issubdtype(ref.dtype, np.integer)
+        got = eng.zoom(m, (H, W), mode=mode, integer=True)
+        assert got.dtype == torch.int32 and tuple(got.shape) == (n, H, W)
+        wrong = int(np.count_nonzero(got.cpu().numpy() != ref))
+        print(f'zoom int32 {case} {mode} n={n}: {wrong} of {ref.size} voxels differ')
+        assert wrong == 0
+
+
+def test_integer_output_is_not_nearest_neighbour_sampling(eng):
+    m, _ = integer_batch(3, 80, 80, 64, 64, 'nearest', seed=5)
+    got = eng.zoom(m, (64, 64), mode='nearest', integer=True).cpu().numpy()
+    nn = np.stack([scipy.ndimage.zoom(m[k], (0.8, 0.8), order=0, mode='nearest') for k in range(3)])
+    assert np.count_nonzero(got != nn) > 0                     # the spline, rounded: scipy's behaviour for the label / skull maps
+
+
+@pytest.mark.parametrize('mode', MODES)
+def test_a_slice_alone_and_inside_a_batch_give_the_same_bits(eng, mode):
+    a = float_batch(70, 217, 181, seed=11)                     # 70 x (217 [+ 24]) rows: the slices straddle the row pass's 64-row groups
+    full = eng.zoom(a, (128, 128), mode=mode).cpu().numpy()
+    for k in (0, 33, 69):
+        alone = eng.zoom(a[k:k + 1], (128, 128), mode=mode).cpu().numpy()
+        assert np.array_equal(alone[0].view(np.uint32), full[k].view(np.uint32))
+
+
+def test_batch_form_is_the_3d_dezoom(eng):
+    vol = np.clip(scipy.ndimage.gaussian_filter(np.random.default_rng(2).random((12, 64, 64)), 1.0), 0, 1).astype(np.float32)
+    ref = scipy.ndimage.zoom(vol.astype(np.float64), (1, 80 / 64, 80 / 64))
+    got = eng.zoom(torch.from_numpy(vol), (80, 80)).cpu().numpy()
+    err = float(np.abs(got - ref).max())
+    print(f'3-D de-zoom 12x64x64 -> 12x80x80: max-abs err {err:.3e}')
+    assert ref.shape == got.shape and err <= F32_BAR
+
+
+def test_bad_arguments_are_refused(eng):
+    with pytest.raises(ValueError):
+        eng.zoom(np.zeros((4, 4), np.float32), (8, 8))
+    with pytest.raises(ValueError):
+        eng.zoom(np.zeros((1, 4, 4), np.float32), (8, 8), mode='reflect')
+    with pytest.raises(ValueError):
+        eng.zoom(np.zeros((1, 1, 4), np.float32), (8, 8))       # a 1-sample line has no spline
+    assert zoom_output_hw((217, 181), (128 / 217, 128 / 181)) == (128, 128)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# end to end
+# ------------------------------------------------------------------------------------------------------------------------------
+class BlurModel:
+    """reconstruct() = a smoothed copy of the input (host), scored by the real engine's device ops."""
+
+    def __init__(self, engine, bs=5):
+        self.engine = engine
+        self.config = types.SimpleNamespace(batchsize=bs)
+        self.network = types.SimpleNamespace(__name__='blur_network')
+        self.model_dir = 'Blur_dSynthetic'
+
+    def reconstruct(self, x, dropout=False, eps=None):
+        x = np.asarray(x, np.float32)
+        rec = scipy.ndimage.uniform_filter(x, size=(1, 9, 9, 1))
+        return {'reconstruction': rec, 'l1err': np.abs(x - rec).sum(), 'l2err': np.abs(x - rec).sum()}
+
+
+def _opts(tmp_path, h=64, **kw):
+    o = get_options(batchsize=5, learningrate=1e-4, numEpochs=3, zDim=64, outputWidth=h, outputHeight=h, slices_start=0, slices_end=12,
+                    config={'CHECKPOINTDIR': str(tmp_path / 'ck'), 'SAMPLEDIR': str(tmp_path / 'smp')})
+    o.update(kw)
+    return o
+
+
+def test_collect_patient_volume_on_the_device_against_the_host_path(eng, tmp_path):
+    ds = SyntheticPatientDataset(n_val=1, n_test=2, slices=14, native=80, h=64, w=64, seed=3, slice_start=2, slice_end=12)
+    for k in ds.get_patient_idx('TEST'):
+        p = ds.patients[k]
+        host = Evaluation.collect_patient_volume(ds, p, p['filtered_files'][0], _opts(tmp_path))
+        dev = Evaluation.collect_patient_volume(ds, p, p['filtered_files'][0], _opts(tmp_path), engine=eng)
+        for a, b in zip(host[:3], dev[:3]):
+            assert a.shape == b.shape and a.dtype == b.dtype
+        err = float(np.abs(host[0] - dev[0]).max())
+        print(f'collect_patient_volume image: max-abs err {err:.3e}')
+        assert err <= F32_BAR
+        assert np.array_equal(host[1], dev[1]) and np.array_equal(host[2], dev[2])
+        assert host[3] == dev[3] and host[4] == dev[4]
+
+
+def test_evaluate_with_device_resampling_and_volume_export(eng, tmp_path):
+    ds = SyntheticPatientDataset(n_val=1, n_test=2, slices=12, native=80, h=64, w=64, seed=1, slice_start=0, slice_end=12)
+    ev_host = Evaluation.evaluate(ds, BlurModel(eng), _opts(tmp_path), epoch='1', description='host')
+    ev_dev = Evaluation.evaluate(ds, BlurModel(eng), _opts(tmp_path, resampleOnDevice=True, exportVolumes=True, threshold=0.05), epoch='1',
+                                 description='device')
+    files = sorted(glob.glob(os.path.join(ev_dev['eval_dir'], 'samples_test_PC', '*.nii.gz')))
+    names = [ds.patients[k]['name'] for k in ds.get_patient_idx('TEST')]
+    assert [os.path.basename(f) for f in files] == sorted([n + '.nii.gz' for n in names] + [n + '.binary.nii.gz' for n in names])
+    vol, _ = nifti.read_nifti(os.path.join(ev_dev['eval_dir'], 'samples_test_PC', names[0] + '.nii.gz'))
+    assert vol.shape == (12, 80, 80) and np.isfinite(vol).all() and vol.max() > 0
+    assert not glob.glob(os.path.join(ev_host['eval_dir'], 'samples_test_PC', '*.nii.gz'))
+    for key in ('diff_AUC', 'diff_AUPRC', 'bestDiceScore'):       # recorded by tools/resample_bench.py, not asserted: the images differ by fp32 rounding
+        print(f'{key}: host {ev_host[key]!r} device {ev_dev[key]!r} difference {ev_dev[key] - ev_host[key]:.3e}')
+
+
+def test_volume_to_slices_on_the_device_against_the_host_call(eng):
+    rng = np.random.default_rng(4)
+    vol = np.clip(scipy.ndimage.gaussian_filter(rng.random((20, 100, 90)), 2.0) * 2.0, 0, None)
+    seg = (scipy.ndimage.gaussian_filter(rng.standard_normal((20, 100, 90)), 3.0) > 0.02).astype(np.float64)
+    kw = dict(slice_start=2, slice_end=18, slice_resolution=(64, 64), skull_stripping=False, empty_thresh=0.0)
+    im_h, lb_h, kept_h = nifti.volume_to_slices(vol, seg, **kw)
+    # the condition on the label input, on scipy alone: the device label map is fp32 before the 0.9 cut, so no resampled value may lie within
+    # the fp32 bar of the cut
+    padded = [np.pad(seg[s], ((0, 0), (5, 5)), 'constant') for s in kept_h]
+    un = np.stack([scipy.ndimage.zoom(p, 64 / 100.0, mode='nearest') for p in padded])
+    assert np.count_nonzero(np.abs(un - 0.9) < F32_BAR) == 0
+    im_d, lb_d, kept_d = nifti.volume_to_slices(vol, seg, engine=eng, **kw)
+    assert kept_d == kept_h and im_d.shape == im_h.shape and im_d.dtype == im_h.dtype and lb_d.dtype == lb_h.dtype
+    err = float(np.abs(im_d.astype(np.float64) - im_h.astype(np.float64)).max())
+    print(f'volume_to_slices images: max-abs err {err:.3e}')
+    assert err <= F32_BAR
+    assert np.array_equal(lb_d, lb_h)

@@ -1,0 +1,202 @@
+"""CPU: the host side of the device slice resampler -- the two C-ABI entries exist in header, ctypes table and library; options['exportVolumes']
+(utils/Evaluation.py:323-334) writes the de-zoomed residual volumes; options['resampleOnDevice'] routes the slice zoom through the engine's
+`zoom` op in three batched calls per patient; and the two facts about scipy.ndimage.zoom the device kernel and its GPU test rest on (the
+integer maps are the spline rounded half away from zero; the GPU test's integer inputs have no voxel near a rounding tie)."""
+import ctypes
+import glob
+import os
+import re
+import types
+
+import numpy as np
+import scipy.ndimage
+import torch
+
+from oracle import scoring as osc
+from unsupervised_anomaly_detection_brain_mri_amd import _lib
+from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation
+from unsupervised_anomaly_detection_brain_mri_amd.utils.default_config_setup import get_options
+from unsupervised_anomaly_detection_brain_mri_amd.utils.nifti import read_nifti
+from unsupervised_anomaly_detection_brain_mri_amd.utils.synthetic import SyntheticPatientDataset
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ('uad_zoom_spline3_workspace', 'uad_zoom_spline3')
+
+
+def test_the_two_entries_are_declared_bound_and_exported():
+    header = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'uad_hip.h')).read(), flags=re.S)
+    declared = set(re.findall(r'\b(uad_[a-z0-9_]+)\s*\(', header))
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ENTRIES:
+        assert name in declared and name in _lib.SYMBOLS and hasattr(lib, name), name
+    ws = lib.uad_zoom_spline3_workspace
+    ws.restype, ws.argtypes = _lib.SYMBOLS['uad_zoom_spline3_workspace']
+    assert ws(110, 217, 181, _lib.ZOOM_CONSTANT) == 110 * 217 * 181 * 8                 # fp64 coefficient planes; host arithmetic only
+    assert ws(110, 217, 181, _lib.ZOOM_NEAREST) == 110 * (217 + 24) * (181 + 24) * 8    # 12 edge-replicated samples a side
+
+
+# ---- the host stand-in engine and blur model of tests/test_evaluation_entry.py ------------------------------------------------------
+class _HostScores:
+    def __init__(self, p, y):
+        self.p, self.y = np.asarray(p, np.float64).reshape(-1), np.asarray(y).reshape(-1).astype(bool)
+        self.auroc, self.auprc, self.positives = osc.auroc(self.p, self.y), osc.average_precision(self.p, self.y), float(self.y.sum())
+
+    def dice_at(self, thresholds):
+        return np.array([osc.dice(self.p > t, self.y) for t in np.atleast_1d(thresholds)])
+
+    def close(self):
+        pass
+
+
+class HostEvalEngine:
+    device = torch.device('cpu')
+
+    def _dev(self, a):
+        return a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.float32))
+
+    def erode_cross(self, masks, iterations=12):
+        return torch.from_numpy(np.stack([osc.binary_erosion_cross(m, iterations) for m in np.asarray(masks)]).astype(np.float32))
+
+    def median3d(self, volume, ksize=5):
+        return torch.from_numpy(osc.median_filter_3d(volume.numpy().astype(np.float64), ksize).astype(np.float32))
+
+    def residual(self, x, x_rec, mask=None, pos_only=True, prior_thresh=None):
+        x, r = np.asarray(x, np.float32), np.asarray(x_rec, np.float32)
+        d = np.maximum(x - r, 0) if pos_only else np.abs(x - r)
+        if mask is not None:
+            d = d * mask.numpy()
+        if prior_thresh is not None:
+            d = np.where(x < np.float32(prior_thresh), 0, d)
+        return torch.from_numpy(d.astype(np.float32)), torch.from_numpy(np.abs(x - r).reshape(len(x), -1).sum(1))
+
+    def scores(self, predictions, labels):
+        return _HostScores(predictions.numpy() if isinstance(predictions, torch.Tensor) else predictions, labels)
+
+    def cc_filter(self, volume, max_voxels=7):
+        return torch.from_numpy(Evaluation.filter_3d_connected_components(volume.numpy(), max_voxels).astype(np.float32))
+
+
+class ZoomingHostEngine(HostEvalEngine):
+    """... plus a scipy-backed `zoom` with engine._EvalOps.zoom's signature that records its calls."""
+
+    def __init__(self):
+        self.zoom_calls = []
+
+    def zoom(self, slices, out_hw, mode='constant', integer=False):
+        s = slices.numpy() if isinstance(slices, torch.Tensor) else np.asarray(slices)
+        self.zoom_calls.append((tuple(s.shape), tuple(out_hw), mode, integer))
+        zf = (out_hw[0] / s.shape[1], out_hw[1] / s.shape[2])
+        out = np.stack([scipy.ndimage.zoom(a.astype(int) if integer else a.astype(np.float64), zf, mode=mode) for a in s])
+        assert out.shape[1:] == tuple(out_hw)
+        return torch.from_numpy(out.astype(np.int32) if integer else out)
+
+
+class BlurModel:
+    def __init__(self, engine, bs=5):
+        self.engine = engine
+        self.config = types.SimpleNamespace(batchsize=bs)
+        self.network = types.SimpleNamespace(__name__='blur_network')
+        self.model_dir = 'Blur_dSynthetic'
+
+    def reconstruct(self, x, dropout=False, eps=None):
+        x = np.asarray(x, np.float32)
+        rec = scipy.ndimage.uniform_filter(x, size=(1, 9, 9, 1))
+        return {'reconstruction': rec, 'l1err': np.abs(x - rec).sum(), 'l2err': np.abs(x - rec).sum()}
+
+
+def _opts(tmp_path, h=64, **kw):
+    o = get_options(batchsize=5, learningrate=1e-4, numEpochs=3, zDim=64, outputWidth=h, outputHeight=h, slices_start=0, slices_end=12,
+                    config={'CHECKPOINTDIR': str(tmp_path / 'ck'), 'SAMPLEDIR': str(tmp_path / 'smp')})
+    o.update(kw)
+    return o
+
+
+def _dataset():
+    return SyntheticPatientDataset(n_val=1, n_test=2, slices=16, native=80, h=64, w=64, seed=1, slice_start=2, slice_end=12)
+
+
+def test_export_volumes_writes_the_dezoomed_residuals(tmp_path):
+    ds = _dataset()
+    sample_dir = str(tmp_path / 'samples')
+    ev, used = Evaluation._evaluate(ds, BlurModel(HostEvalEngine()), sample_dir, _opts(tmp_path, exportVolumes=True), split='TEST')
+    names = [ds.patients[k]['name'] for k in ds.get_patient_idx('TEST')]
+    assert [p['name'] for p in used] == names
+    assert sorted(os.path.basename(f) for f in glob.glob(os.path.join(sample_dir, '*'))) == sorted(n + '.nii.gz' for n in names)   # 'bestdice': no binary file
+    assert ev['diffs'].max() > 0
+    for k, name in enumerate(names):
+        vol, hdr = read_nifti(os.path.join(sample_dir, name + '.nii.gz'))
+        assert vol.shape == (16, 80, 80)                                  # the native volume's
+        assert np.all(vol[:2] == 0) and np.all(vol[12:] == 0)             # outside [sliceStart, sliceEnd): exactly zero
+        diffs = ev['diffs'][10 * k:10 * (k + 1)]
+        want = scipy.ndimage.zoom(diffs, (1, 80 / 64, 80 / 64))
+        assert want.shape == (10, 80, 80)
+        np.testing.assert_array_equal(vol[2:12], want.astype(np.float32).astype(np.float64))      # the fp32 file round trip
+
+
+def test_export_volumes_adds_the_binary_file_for_a_float_threshold_and_nothing_when_off(tmp_path):
+    ds = _dataset()
+    names = [ds.patients[k]['name'] for k in ds.get_patient_idx('TEST')]
+    d_on, d_off = str(tmp_path / 'on'), str(tmp_path / 'off')
+    Evaluation._evaluate(ds, BlurModel(HostEvalEngine()), d_on, _opts(tmp_path, exportVolumes=True, threshold=0.001), split='TEST')
+    assert sorted(os.path.basename(f) for f in glob.glob(os.path.join(d_on, '*'))) == sorted([n + '.nii.gz' for n in names] + [n + '.binary.nii.gz' for n in names])
+    marked = 0
+    for n in names:
+        vol, _ = read_nifti(os.path.join(d_on, n + '.nii.gz'))
+        binary, _ = read_nifti(os.path.join(d_on, n + '.binary.nii.gz'))
+        np.testing.assert_array_equal(binary, (vol > 0.001).astype(np.float64))
+        marked += int(binary.sum())
+    assert 0 < marked < 2 * binary.size
+    Evaluation._evaluate(ds, BlurModel(HostEvalEngine()), d_off, _opts(tmp_path, exportVolumes=False, threshold=0.001), split='TEST')
+    assert glob.glob(os.path.join(d_off, '*')) == []
+    ev = Evaluation.evaluate(ds, BlurModel(HostEvalEngine()), _opts(tmp_path, exportVolumes=True), epoch='2', description='export')   # through the public entry
+    assert len(glob.glob(os.path.join(ev['eval_dir'], 'samples_test_PC', '*.nii.gz'))) == 2
+
+
+def test_resample_on_device_makes_three_batched_zoom_calls_per_patient(tmp_path):
+    ds = _dataset()
+    eng = ZoomingHostEngine()
+    ev_d, _ = Evaluation._evaluate(ds, BlurModel(eng), str(tmp_path / 'd'), _opts(tmp_path, resampleOnDevice=True), split='TEST')
+    per_patient = [((10, 80, 80), (64, 64), 'constant', False), ((10, 80, 80), (64, 64), 'nearest', True), ((10, 80, 80), (64, 64), 'nearest', True)]
+    assert eng.zoom_calls == per_patient * 2
+    host = ZoomingHostEngine()
+    ev_h, _ = Evaluation._evaluate(ds, BlurModel(host), str(tmp_path / 'h'), _opts(tmp_path), split='TEST')
+    assert host.zoom_calls == []                                          # without the option the op is never called
+    for key in ('x', 'labelmaps', 'diffs'):
+        assert ev_d[key].shape == ev_h[key].shape and ev_d[key].dtype == ev_h[key].dtype
+        np.testing.assert_array_equal(ev_d[key], ev_h[key])
+    # the export's de-zoom goes through the op too when opted in: one more call per patient, on the [S,64,64] residual sub-volume
+    eng.zoom_calls.clear()
+    Evaluation._evaluate(ds, BlurModel(eng), str(tmp_path / 'e'), _opts(tmp_path, resampleOnDevice=True, exportVolumes=True), split='TEST')
+    assert eng.zoom_calls == (per_patient + [((10, 64, 64), (80, 80), 'constant', False)]) * 2
+    assert 'resampleOnDevice' not in get_options(batchsize=5, learningrate=1e-4, numEpochs=3, zDim=64, outputWidth=64, outputHeight=64, slices_start=0,
+                                                 slices_end=12, config={'CHECKPOINTDIR': str(tmp_path / 'ck'), 'SAMPLEDIR': str(tmp_path / 'smp')})
+
+
+# ---- scipy facts ----------------------------------------------------------------------------------------------------------------
+def _binary_masks(n, h, w, seed):
+    f = scipy.ndimage.gaussian_filter(np.random.default_rng(seed).standard_normal((n, h, w)), (0, 4, 4))
+    return (f > np.quantile(f, 0.6)).astype(int)
+
+
+def test_scipy_integer_zoom_is_the_spline_rounded_half_away_from_zero():
+    m = _binary_masks(20, 217, 181, seed=0) * 3 - 1                       # values -1 / 2: both branches of the rounding
+    zf = (128 / 217, 128 / 181)
+    for mode in ('constant', 'nearest'):
+        for a in m:
+            t = scipy.ndimage.zoom(a.astype(np.float64), zf, mode=mode)
+            want = np.where(t > 0, (t + 0.5).astype(np.int64), (t - 0.5).astype(np.int64))         # the cast truncates towards zero
+            np.testing.assert_array_equal(scipy.ndimage.zoom(a, zf, mode=mode), want)
+        nn = scipy.ndimage.zoom(m[0], zf, order=0, mode=mode)
+        assert np.count_nonzero(nn != scipy.ndimage.zoom(m[0], zf, mode=mode)) > 0                  # not nearest-neighbour sampling
+
+
+def test_binary_masks_have_no_voxel_near_a_rounding_tie():
+    """The condition under which the GPU test may demand exact equality of the int32 output: scipy's unrounded value is nowhere within 1e-9 of a
+    half-integer, on scipy alone."""
+    m = _binary_masks(20, 217, 181, seed=1)
+    total = ties = 0
+    for a in m:
+        t = scipy.ndimage.zoom(a.astype(np.float64), (128 / 217, 128 / 181), mode='nearest')
+        ties += int(np.count_nonzero(np.abs(np.abs(t - np.floor(t)) - 0.5) < 1e-9))
+        total += t.size
+    assert total == 20 * 128 * 128 and ties == 0

@@ -52,6 +52,8 @@ class UadGanIO(C.Structure):
                                           'l1_map', 'scalars', 'eps', 'mask_sigma', 'eps_w', 'mask_w_mu', 'mask_w_ls', 'x_ce', 'l1_map_ce', 'anomaly')]
 
 
+ZOOM_CONSTANT, ZOOM_NEAREST = 0, 1
+ZOOM_F32, ZOOM_I32 = 0, 1
 GAN_ENCODER, GAN_GENERATOR, GAN_DISCRIMINATOR = 0, 1, 2
 GAN_UNIFIED, GAN_RESNET, GAN_ANOVAEGAN, GAN_AAE = 0, 1, 2, 3
 GAN_GROUP_VAE = 3
@@ -123,6 +125,9 @@ SYMBOLS = {
     'uad_scores_threshold_at_precision': (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
     'uad_cc_label': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'uad_detection_rate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_zoom_spline3_workspace': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'uad_zoom_spline3': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
     'uad_rng_fill': (C.c_int, [C.POINTER(UadRngJob), C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_void_p]),
     'uad_clock_probe': (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_void_p]),
     'uad_gan_create': (C.c_int, [C.POINTER(UadGanConfig), C.POINTER(C.c_void_p)]),

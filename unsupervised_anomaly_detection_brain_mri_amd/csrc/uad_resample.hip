@@ -1,0 +1,238 @@
+// Cubic-spline slice resampling on the device: scipy.ndimage.zoom(order=3, prefilter=True, grid_mode=False) per [h,w] slice of a batch
+// (reference utils/Evaluation.py:223-232 -- three zoom calls per slice on the host -- and :323-334, the exportVolumes de-zoom).
+//   1. zoom_cols_kernel   fp32 -> fp64, edge-replicated padding ('nearest': 12 samples a side), gain 6 and the causal / anticausal
+//                         recursion (pole sqrt(3) - 2) along y: one thread per (slice, padded x), coalesced across x.
+//   2. zoom_rows_kernel   the same recursion along x: one wave owns 64 rows and walks them in 64-column tiles staged through LDS, so
+//                         that global accesses stay row-contiguous; each lane carries its row's recursion state from tile to tile.
+//   3. zoom_interp_kernel one thread per output pixel: 4 x 4 taps of the fp64 coefficient plane (L2-resident), fp32 or rounded int32 out.
+// All arithmetic is fp64 and written in scipy's order of operations (ni_splines.c, ni_interpolation.c: NI_ZoomShift) without fused
+// multiply-adds, because the integer maps must round as scipy rounds them.  Latency- and bandwidth-shaped work: no matrix cores, no
+// atomics (a slice's bits do not depend on the batch around it), vector stores only.
+// tests/native/resample_emu.cpp compiles the kernels of this file for the HOST (UAD_RESAMPLE_HOST_EMULATION: a shim supplies threadIdx & co.,
+// the launch layer at the end of the file is left out), so that their arithmetic is checked against scipy without a GPU.
+#include <cmath>
+
+#ifndef UAD_RESAMPLE_HOST_EMULATION
+#include "uad_kernels.h"
+#endif
+#include "../../include/uad_hip.h"
+
+#pragma clang fp contract(off)
+
+#ifndef UAD_RESAMPLE_HOST_EMULATION
+int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
+#define fail uad_fail
+#endif
+
+#define RS_TRY(expr)                                                                              \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
+    } while (0)
+
+namespace {
+
+constexpr int ZOOM_PAD = 12;       // scipy.ndimage._interpolation._prepad_for_spline_filter: npad of mode 'nearest'
+constexpr int ZOOM_HORIZON = 48;   // |z|^48 = 3.5e-28: on longer lines the mirrored sum of the causal initial value stops here
+constexpr int ZOOM_TILE = 64;
+static_assert(ZOOM_HORIZON <= ZOOM_TILE, "the row pass takes its initial value from the first tile");
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ni_interpolation.c: the mirror extension of a tap index (NI_ZoomShift's edge offsets), len >= 2
+__device__ __forceinline__ int mirror_index(int idx, int len) {
+    const int s2 = 2 * len - 2;
+    if (idx < 0) {
+        idx = s2 * (-idx / s2) + idx;
+        idx = idx <= 1 - len ? idx + s2 : -idx;
+    } else if (idx >= len) {
+        idx -= s2 * (idx / s2);
+        if (idx >= len) idx = s2 - idx;
+    }
+    return idx;
+}
+
+// ni_splines.c _init_causal_mirror over a line given by an accessor (already multiplied by the gain); zn = z^(len-1).
+// len > ZOOM_HORIZON: the terms past the horizon (and every z^(len-1) term) are below fp64 round-off and are left out.
+template <class F>
+__device__ __forceinline__ double causal_init(F at, int len, double z, double zn) {
+    double zi = z;
+    if (len > ZOOM_HORIZON) {
+        double s = at(0);
+        for (int i = 1; i < ZOOM_HORIZON; ++i) { s += zi * at(i); zi *= z; }
+        return s;
+    }
+    double s = at(0) + zn * at(len - 1);
+    for (int i = 1; i < len - 1; ++i) { s += zi * (at(i) + zn * at(len - 1 - i)); zi *= z; }
+    return s / (1 - zn * zn);
+}
+
+__global__ void __launch_bounds__(256) zoom_cols_kernel(const float* __restrict__ in, int n, int h, int w, int pad, int hp, int wp, double z,
+                                                        double zn, double* __restrict__ coef) {
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (size_t)n * wp) return;
+    const int slice = (int)(gid / wp), xq = (int)(gid % wp);
+    const float* src = in + (size_t)slice * h * w + clampi(xq - pad, 0, w - 1);
+    double* dst = coef + (size_t)slice * hp * wp + xq;
+    auto at = [&](int yq) { return (double)src[(size_t)clampi(yq - pad, 0, h - 1) * w] * 6.0; };
+    double prev = causal_init(at, hp, z, zn), prev2 = prev;
+    dst[0] = prev;
+    for (int y = 1; y < hp; ++y) {
+        prev2 = prev;
+        prev = at(y) + z * prev;
+        dst[(size_t)y * wp] = prev;
+    }
+    double nxt = (z * prev2 + prev) * z / (z * z - 1);
+    dst[(size_t)(hp - 1) * wp] = nxt;
+    for (int y = hp - 2; y >= 0; --y) {
+        nxt = z * (nxt - dst[(size_t)y * wp]);
+        dst[(size_t)y * wp] = nxt;
+    }
+}
+
+// rows: the [n * hp] lines of length wp of the coefficient planes, contiguous.  One wave per 64 rows; tile[r][c] with a leading dimension
+// of 65 doubles keeps both the row-wise staging (lane = column) and the recursion (lane = row) free of LDS bank conflicts.
+__global__ void __launch_bounds__(ZOOM_TILE) zoom_rows_kernel(double* __restrict__ coef, int rows, int wp, double z, double zn) {
+    __shared__ double tile[ZOOM_TILE][ZOOM_TILE + 1];
+    const int lane = threadIdx.x;
+    const int r0 = blockIdx.x * ZOOM_TILE;
+    const int nr = rows - r0 < ZOOM_TILE ? rows - r0 : ZOOM_TILE;
+    const int ntiles = (wp + ZOOM_TILE - 1) / ZOOM_TILE;
+    double* base = coef + (size_t)r0 * wp;
+    double prev = 0.0, prev2 = 0.0, nxt = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {                       // 0: causal, tiles left to right; 1: anticausal, right to left
+        for (int jj = 0; jj < ntiles; ++jj) {
+            const int j = pass == 0 ? jj : ntiles - 1 - jj;
+            const int c0 = j * ZOOM_TILE;
+            const int nc = wp - c0 < ZOOM_TILE ? wp - c0 : ZOOM_TILE;
+            const double gain = pass == 0 ? 6.0 : 1.0;           // scipy scales the line by the filter gain before the causal sweep
+            if (lane < nc)
+                for (int r = 0; r < nr; ++r) tile[r][lane] = base[(size_t)r * wp + c0 + lane] * gain;
+            __syncthreads();
+            if (lane < nr) {
+                double* row = tile[lane];
+                if (pass == 0) {
+                    int k = 0;
+                    if (j == 0) {
+                        prev = causal_init([&](int i) { return row[i]; }, wp, z, zn);
+                        prev2 = prev;
+                        row[0] = prev;
+                        k = 1;
+                    }
+                    for (; k < nc; ++k) {
+                        prev2 = prev;
+                        prev = row[k] + z * prev;
+                        row[k] = prev;
+                    }
+                } else {
+                    int k = nc - 1;
+                    if (j == ntiles - 1) {
+                        nxt = (z * prev2 + prev) * z / (z * z - 1);
+                        row[k] = nxt;
+                        --k;
+                    }
+                    for (; k >= 0; --k) {
+                        nxt = z * (nxt - row[k]);
+                        row[k] = nxt;
+                    }
+                }
+            }
+            __syncthreads();
+            if (lane < nc)
+                for (int r = 0; r < nr; ++r) base[(size_t)r * wp + c0 + lane] = tile[r][lane];
+            __syncthreads();
+        }
+    }
+}
+
+// NI_ZoomShift for one axis: output sample o -> first tap, the four (mirror-folded) tap indices and the cubic B-spline weights
+// (ni_splines.c get_spline_interpolation_weights, order 3)
+// Returns false where scipy writes cval: the product o * zoom of the LAST sample can round to just above len - 1 (128 -> 181: 180 * (127 / 180) =
+// 127.00000000000001), which mode 'constant' treats as outside the line -- that output column / row is 0 in scipy, and here.  ('nearest' reads
+// the padded plane, where the coordinate is inside.)
+__device__ __forceinline__ bool zoom_taps(int o, double zoom, int pad, int len, int idx[4], double wt[4]) {
+    double cc = (double)o * zoom;
+    cc += (double)pad;
+    const bool inside = cc <= (double)(len - 1);
+    const double fl = floor(cc);
+    const int start = (int)fl - 1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) idx[k] = mirror_index(start + k, len);
+    const double y = cc - fl, zc = 1.0 - y;
+    wt[1] = (y * y * (y - 2.0) * 3.0 + 4.0) / 6.0;
+    wt[2] = (zc * zc * (zc - 2.0) * 3.0 + 4.0) / 6.0;
+    wt[0] = zc * zc * zc / 6.0;
+    wt[3] = 1.0 - wt[0] - wt[1] - wt[2];
+    return inside;
+}
+
+__global__ void __launch_bounds__(256) zoom_interp_kernel(const double* __restrict__ coef, int n, int pad, int hp, int wp, int H, int W, double zy,
+                                                          double zx, int out_kind, void* __restrict__ out) {
+    const int X = blockIdx.x * 64 + threadIdx.x;
+    const int Y = blockIdx.y * 4 + threadIdx.y;
+    if (X >= W || Y >= H) return;
+    int iy[4], ix[4];
+    double wy[4], wx[4];
+    const bool inside_y = zoom_taps(Y, zy, pad, hp, iy, wy);
+    const bool inside = zoom_taps(X, zx, pad, wp, ix, wx) && inside_y;
+    for (int s = blockIdx.z; s < n; s += gridDim.z) {
+        const double* c = coef + (size_t)s * hp * wp;
+        double t = 0.0;
+        if (inside) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double* row = c + (size_t)iy[i] * wp;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) t += row[ix[j]] * wy[i] * wx[j];
+            }
+        }
+        const size_t o = ((size_t)s * H + Y) * W + X;
+        if (out_kind == UAD_ZOOM_I32) ((int*)out)[o] = t > 0 ? (int)(t + 0.5) : (int)(t - 0.5);
+        else ((float*)out)[o] = (float)t;
+    }
+}
+
+inline int zoom_pad(int boundary) { return boundary == UAD_ZOOM_NEAREST ? ZOOM_PAD : 0; }
+
+}  // namespace
+
+#ifndef UAD_RESAMPLE_HOST_EMULATION
+extern "C" {
+
+size_t uad_zoom_spline3_workspace(int n, int h, int w, int boundary) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    const int pad = zoom_pad(boundary);
+    return (size_t)n * (size_t)(h + 2 * pad) * (size_t)(w + 2 * pad) * sizeof(double);
+}
+
+int uad_zoom_spline3(const float* in, int n, int h, int w, int H, int W, int boundary, int out_kind, void* out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    if (!in || !out || !workspace || n <= 0 || H <= 0 || W <= 0) return fail(UAD_ERR_INVALID, "zoom_spline3: bad arguments");
+    if (h < 2 || w < 2) return fail(UAD_ERR_INVALID, "zoom_spline3: a line needs at least 2 samples, got %dx%d", h, w);
+    if (boundary != UAD_ZOOM_CONSTANT && boundary != UAD_ZOOM_NEAREST) return fail(UAD_ERR_INVALID, "zoom_spline3: unknown boundary %d", boundary);
+    if (out_kind != UAD_ZOOM_F32 && out_kind != UAD_ZOOM_I32) return fail(UAD_ERR_INVALID, "zoom_spline3: unknown out_kind %d", out_kind);
+    const int pad = zoom_pad(boundary), hp = h + 2 * pad, wp = w + 2 * pad;
+    if ((size_t)n * hp > 0x7fffffffULL || (size_t)n * wp > 0x7fffffffULL || (size_t)H * W > 0x7fffffffULL)
+        return fail(UAD_ERR_UNSUPPORTED, "zoom_spline3: batch too large");
+    if ((H + 3) / 4 > 65535) return fail(UAD_ERR_UNSUPPORTED, "zoom_spline3: output too tall");
+    const size_t need = uad_zoom_spline3_workspace(n, h, w, boundary);
+    if (workspace_bytes < need) return fail(UAD_ERR_INVALID, "zoom_spline3: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (((size_t)workspace & 15) != 0) return fail(UAD_ERR_INVALID, "zoom_spline3: workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    double* coef = (double*)workspace;
+    const double z = std::sqrt(3.0) - 2.0;                      // ni_splines.c get_filter_poles, order 3
+    const double zy = H > 1 ? (double)(h - 1) / (double)(H - 1) : 1.0, zx = W > 1 ? (double)(w - 1) / (double)(W - 1) : 1.0;
+    const size_t cols = (size_t)n * wp;
+    hipLaunchKernelGGL(zoom_cols_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, in, n, h, w, pad, hp, wp, z, std::pow(z, hp - 1), coef);
+    RS_TRY(hipGetLastError());
+    const int rows = n * hp;
+    hipLaunchKernelGGL(zoom_rows_kernel, dim3((unsigned)((rows + ZOOM_TILE - 1) / ZOOM_TILE)), dim3(ZOOM_TILE), 0, st, coef, rows, wp, z, std::pow(z, wp - 1));
+    RS_TRY(hipGetLastError());
+    const dim3 grid((W + 63) / 64, (H + 3) / 4, n < 65535 ? n : 65535);
+    hipLaunchKernelGGL(zoom_interp_kernel, grid, dim3(64, 4), 0, st, (const double*)coef, n, pad, hp, wp, H, W, zy, zx, out_kind, out);
+    RS_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+}  // extern "C"
+#endif  // UAD_RESAMPLE_HOST_EMULATION

@@ -67,6 +67,12 @@ def shader_clock_under(enqueue, window_ms=30.0, device=None):
     return cyc / max(ticks, 1) / 10.0
 
 
+def zoom_output_hw(in_hw, factors):
+    """The output shape scipy.ndimage.zoom gives a [h,w] slice: round(h * zoom) per axis (one factor serves both axes)."""
+    f = (factors, factors) if np.isscalar(factors) else tuple(factors)
+    return tuple(int(round(i * z)) for i, z in zip(in_hw, f))
+
+
 class _EvalOps:
     """Model-independent device ops of the evaluation path (erosion, 3-D median, residual maps, sort-based metrics); shared by
     the AE-family Engine and the f-AnoGAN GanEngine.  Needs self.lib, self.device, self._dev, self._stream."""
@@ -89,6 +95,29 @@ class _EvalOps:
             raise ValueError(f'volume must be [D,H,W], got {tuple(v.shape)}')
         out = torch.empty_like(v)
         _lib.check(self.lib.uad_median3d(_ptr(v), v.shape[0], v.shape[1], v.shape[2], int(ksize), _ptr(out), self._stream()))
+        return out
+
+    def zoom(self, slices, out_hw, mode='constant', integer=False):
+        """scipy.ndimage.zoom(s, (H/h, W/w), order=3, mode=mode) of every slice of a [n,h,w] array / tensor on the device (uad_zoom_spline3;
+        utils/Evaluation.py:223-232, 323-334).  out_hw = (H, W): the caller computes the shape as scipy does (zoom_output_hw).  mode 'constant'
+        (cval 0) | 'nearest'.  integer=False -> fp32 tensor [n,H,W]; integer=True -> int32, the spline value rounded half away from zero,
+        which is what scipy returns for an integer-typed label / skull map."""
+        if mode not in ('constant', 'nearest'):
+            raise ValueError(f"zoom mode must be 'constant' or 'nearest', got {mode!r}")
+        s = slices if isinstance(slices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(slices, np.float32))
+        s = s.to(self.device, torch.float32).contiguous()
+        if s.dim() != 3:
+            raise ValueError(f'slices must be [n,h,w], got {tuple(s.shape)}')
+        n, h, w = s.shape
+        H, W = (int(v) for v in out_hw)
+        out = torch.empty((n, H, W), device=self.device, dtype=torch.int32 if integer else torch.float32)
+        if n == 0:
+            return out
+        boundary = _lib.ZOOM_NEAREST if mode == 'nearest' else _lib.ZOOM_CONSTANT
+        nbytes = int(self.lib.uad_zoom_spline3_workspace(n, h, w, boundary))
+        ws = torch.empty(max(nbytes // 8, 1), device=self.device, dtype=torch.float64)       # stream-ordered caching allocator: safe to drop after the launch
+        _lib.check(self.lib.uad_zoom_spline3(_ptr(s), n, h, w, H, W, boundary, _lib.ZOOM_I32 if integer else _lib.ZOOM_F32, _ptr(out), _ptr(ws),
+                                             nbytes, self._stream()))
         return out
 
     def mc_stats(self, recs, mask=None):

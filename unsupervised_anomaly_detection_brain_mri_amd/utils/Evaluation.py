@@ -2,7 +2,7 @@
 description)` (:372-526), `_evaluate(datasetObj, modelObj, sampleDir, options, split)` (:183-365) and
 `determine_threshold_on_labeled_patients(dataset_pc, model, options, epoch, description)` (:529-570) on the dataset duck-type
 (`patients`, `get_patient_idx`, `load_volume_and_groundtruth`, `options.{sliceStart, sliceEnd, axis, sliceResolution}`), over the
-array-level core `evaluate_arrays` / `evaluate_volume` (PNG / PDF / NIfTI export dropped).  Everything between the reconstruction and the scalar metrics stays on the device:
+array-level core `evaluate_arrays` / `evaluate_volume` (PNG / PDF export dropped; options['exportVolumes'] writes the NIfTI volumes).  Everything between the reconstruction and the scalar metrics stays on the device:
 slices of a volume are reconstructed in ONE batched call (the reference runs one sess.run per slice, :246-250), the brain
 masks are eroded (uad_erode_cross), residual map + mask + hyper-intensity prior come from uad_residual, the 5x5x5 median is
 uad_median3d, and AUROC / AUPRC / the Dice threshold sweep read one device sort of all voxels (uad_scores_*).
@@ -317,11 +317,17 @@ def _zoom_factor(resolution, shape):
     return tuple(i / j for (i, j) in zip(resolution, shape))
 
 
-def collect_patient_volume(datasetObj, patient, nii_filename, options):
+def _zoom_output_hw(shape, zf):
+    return tuple(int(round(i * z)) for i, z in zip(shape, zf))          # scipy.ndimage.zoom's output shape
+
+
+def collect_patient_volume(datasetObj, patient, nii_filename, options, engine=None):
     """utils/Evaluation.py:205-232: load the volume, its ground truth and skull map; take slices sliceStart .. min(sliceEnd, #slices) along
     options.axis; zoom every slice to options.sliceResolution -- cubic spline for the image (scipy.ndimage.zoom default order 3), the same
     call with mode='nearest' for the integer label / skull maps, exactly as written there.  Returns (x [S,H,W] float64, seg [S,H,W] int,
-    skullmap [S,H,W] int, prior_quantile of the whole loaded volume, slice indices) or None when the volume is too thin (:210-211)."""
+    skullmap [S,H,W] int, prior_quantile of the whole loaded volume, slice indices) or None when the volume is too thin (:210-211).
+    engine: an engine with the device `zoom` op (engine._EvalOps.zoom) -- the three maps of the patient are stacked and resampled in three
+    batched device calls (image: 'constant', fp32; label / skull: 'nearest', int32) and downloaded; None = the host loop above."""
     o = datasetObj.options
     nii, nii_seg, nii_skullmap = datasetObj.load_volume_and_groundtruth(nii_filename, patient)
     prior_quantile = np.quantile(nii.data, 0.9)
@@ -330,6 +336,17 @@ def collect_patient_volume(datasetObj, patient, nii_filename, options):
     slice_start = o.sliceStart if o.sliceStart else 0
     n_ax = nii.num_slices_along_axis(o.axis)
     slice_end = min(o.sliceEnd, n_ax) if o.sliceEnd else n_ax
+    if engine is not None and o.sliceResolution is not None and slice_end > slice_start:
+        idx = list(range(slice_start, slice_end))
+        xs = np.stack([nii.get_slice(s, o.axis) for s in idx])
+        segs = np.stack([nii_seg.get_slice(s, o.axis).astype(int) for s in idx])
+        skulls = np.stack([nii_skullmap.get_slice(s, o.axis).astype(int) for s in idx])
+        hw = _zoom_output_hw(xs.shape[1:], _zoom_factor(o.sliceResolution, xs.shape[1:]))
+        x = engine.zoom(xs, hw, mode='constant', integer=False)
+        seg = engine.zoom(segs, hw, mode='nearest', integer=True)
+        skull = engine.zoom(skulls, hw, mode='nearest', integer=True)
+        return (x.cpu().numpy().astype(np.float64), seg.cpu().numpy().astype(segs.dtype), skull.cpu().numpy().astype(skulls.dtype),
+                float(prior_quantile), idx)
     xs, segs, skulls, idx = [], [], [], []
     for s in range(slice_start, slice_end):
         slice_data = nii.get_slice(s, o.axis)
@@ -344,11 +361,57 @@ def collect_patient_volume(datasetObj, patient, nii_filename, options):
     return np.asarray(xs, np.float64), np.asarray(segs), np.asarray(skulls), float(prior_quantile), idx
 
 
+def _is_float(v):
+    try:
+        float(v)
+        return True
+    except (TypeError, ValueError):
+        return False
+
+
+def export_patient_volume(datasetObj, patient, nii_filename, subvolume, idx, sampleDir, options, engine=None):
+    """options['exportVolumes'] (utils/Evaluation.py:323-334): de-zoom the post-processed residual sub-volume [S,H,W] back to the native slice
+    resolution with the factor (1,) + 1 / zoom_factor (cubic spline, scipy.ndimage.zoom's defaults; the device op when `engine` is given --
+    factor 1 on axis 0 makes it a batch of 2-D zooms), put slice k back where get_slice(idx[k], axis) read it from in a zeroed float64 array
+    of the native shape, and write <sampleDir>/<patient name>.nii.gz; when options['threshold'] parses as a float also
+    <patient name>.binary.nii.gz of `> threshold`.  The reference walks sliceStart .. sliceEnd even past the volume's end and would raise
+    there; here the loop is clipped to the collected indices `idx`.  Origin and direction are not carried (write_nifti writes pixdim only).
+    Returns the list of files written."""
+    import os
+    from .nifti import write_nifti
+    o = datasetObj.options
+    nii = datasetObj.load_volume_and_groundtruth(nii_filename, patient)[0]
+    native = np.zeros(nii.shape(), np.float64)
+    ax = {'axial': 0, 'coronal': 1, 'sagittal': 2, 'saggital': 2}.get(o.axis, o.axis)
+    sub = subvolume.detach().cpu().numpy() if isinstance(subvolume, torch.Tensor) else np.asarray(subvolume)
+    if o.sliceResolution is not None:
+        slice_shape = nii.get_slice(idx[0], o.axis).shape
+        zf = _zoom_factor(o.sliceResolution, slice_shape)
+        dezoom = (1,) + tuple(1 / np.asarray(zf))
+        if engine is not None:
+            hw = _zoom_output_hw(sub.shape[1:], dezoom[1:])
+            sub = engine.zoom(subvolume, hw, mode='constant', integer=False).cpu().numpy()
+        else:
+            sub = scipy.ndimage.zoom(sub.astype(np.float64), dezoom)
+    where = [slice(None)] * 3
+    for k, s in enumerate(idx):
+        where[ax] = s
+        native[tuple(where)] = sub[k]
+    files = [os.path.join(sampleDir, '{}.nii.gz'.format(patient['name']))]
+    write_nifti(files[0], native)
+    thr = options.get('threshold')
+    if thr and not isinstance(thr, bool) and _is_float(thr):
+        files.append(os.path.join(sampleDir, '{}.binary.nii.gz'.format(patient['name'])))
+        write_nifti(files[1], (native > float(thr)).astype(np.float32))
+    return files
+
+
 def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
     """utils/Evaluation.py:183-365.  Walks the split's patients through the dataset duck-type, reconstructs every patient's slice stack in
     batched device calls and returns (eval_dict, patients): eval_dict['diffs'] [P*S,H,W] post-processed residuals (device tensor under
     '_diffs_device' as well), 'labelmaps', 'x', 'l1reconstructionErrors' and their mean / variance.  The per-slice PNG dumps are not
-    written (sampleDir is created like the reference does)."""
+    written (sampleDir is created like the reference does).  options['resampleOnDevice']: the slice zoom (and the exportVolumes de-zoom)
+    run on the device spline op instead of scipy; options['exportVolumes']: export_patient_volume per patient."""
     import os
     os.makedirs(sampleDir, exist_ok=True)
     print("Testing {} samples...".format(datasetObj.num_batches(1, set=split)))
@@ -358,6 +421,9 @@ def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
     variances = []               # numMonteCarloSamples > 1: every patient's epistemic-variance volume (utils/Evaluation.py:238-266,404-408)
     mc = int(options.get('numMonteCarloSamples') or 0) > 1
     used = []
+    zoom_engine = modelObj.engine if should(options, 'resampleOnDevice') else None      # opt-in: the default stays the host scipy path
+    if zoom_engine is not None and not hasattr(zoom_engine, 'zoom'):
+        raise RuntimeError("options['resampleOnDevice'] needs an engine with the device zoom op")
 
     def one(p):
         patient = patients[p]
@@ -365,14 +431,17 @@ def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
         if type(files) is not list:
             files = [files]
         for nii_filename in files:                               # `if len(_eval_dict['diffs']) == 0` (:203): the first usable file of a patient
-            got = collect_patient_volume(datasetObj, patient, nii_filename, options)
+            got = collect_patient_volume(datasetObj, patient, nii_filename, options, engine=zoom_engine)
             if got is None:
                 continue
-            x, seg, skull, prior_q, _ = got
+            x, seg, skull, prior_q, idx = got
             t0 = time.time()
             d, l1 = evaluate_volume(modelObj, x, skull, options, eps, device_out=True, prior=prior_q)
             rec = {'x': x, 'seg': seg, 'l1': list(l1), 'time': (time.time() - t0) / max(len(x), 1),
                    'var': modelObj.last_epistemic_variance.cpu().numpy() if mc else None}
+            if should(options, 'exportVolumes') and _dp_rank_world()[0] == 0:
+                # one() runs on the patient's owner (_sharded_map): rank 0 writes the files of the patients of its own shard, the other ranks write none
+                export_patient_volume(datasetObj, patient, nii_filename, d, idx, sampleDir, options, engine=zoom_engine)
             return d, rec
         return None
     # patients are sharded over the ranks of an initialised process group (module docstring); every rank ends up with the full, ordered list

@@ -144,10 +144,12 @@ def crop_center(img, cropx, cropy):
 
 
 def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0, slice_end=155, slice_resolution=None, skull_stripping=True,
-                     view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None):
+                     view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None):
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
-    map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210)."""
+    map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
+    engine: an engine with the device `zoom` op (engine._EvalOps.zoom): the kept, padded slices are resampled in one batched device call each
+    for the image ('constant') and the label map ('nearest', fp32, then >= 0.9) instead of two scipy calls per slice."""
     from scipy.ndimage import rotate, zoom
     if denoise:
         raise NotImplementedError("nii.denoise() is SimpleITK's CurvatureFlow filter (MSLUB.py:257); it is not restated here")
@@ -161,7 +163,7 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     if skull_stripping and brainmask is not None:
         vol = vol * (np.asarray(brainmask) >= 0.1)                          # NII.apply_skullmap
     vol = normalize_scaling(vol)
-    imgs, labs, kept = [], [], []
+    sds, sss, kept_s = [], [], []
     for s in range(slice_start, min(slice_end, vol.shape[ax])):
         idx = [slice(None)] * 3
         idx[ax] = s
@@ -175,9 +177,18 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
             if py != (0, 0) or px != (0, 0):
                 sd = np.pad(sd, (py, px), 'constant'); ss = np.pad(ss, (py, px), 'constant')
             f = float(H) / float(sd.shape[0])                               # one factor for both axes, as the reference (:179-180)
-            sd = zoom(sd, f)
-            ss = zoom(ss, f, mode='nearest')
-            ss = (ss >= 0.9).astype(np.float64)
+            if engine is None:
+                sd = zoom(sd, f)
+                ss = zoom(ss, f, mode='nearest')
+                ss = (ss >= 0.9).astype(np.float64)
+        sds.append(sd); sss.append(ss); kept_s.append(s)
+    if engine is not None and slice_resolution is not None and sds:
+        f = float(slice_resolution[0]) / float(sds[0].shape[0])
+        hw = tuple(int(round(i * f)) for i in sds[0].shape)                 # scipy.ndimage.zoom's output shape
+        sds = list(engine.zoom(np.stack(sds), hw, mode='constant').cpu().numpy())
+        sss = list((engine.zoom(np.stack(sss), hw, mode='nearest').cpu().numpy().astype(np.float64) >= 0.9).astype(np.float64))
+    imgs, labs, kept = [], [], []
+    for sd, ss, s in zip(sds, sss, kept_s):
         for angle in rotations:
             sdr, ssr = (sd, ss) if angle == 0 else (rotate(sd, angle, reshape=False), rotate(ss, angle, reshape=False, mode='nearest'))
             if center_crop is not None:
@@ -202,9 +213,9 @@ def partition_patients(n_patients, partition=None, rng=None):
     return out
 
 
-def build_cache(directory, patients, partition=None, seed=0, **slice_options):
+def build_cache(directory, patients, partition=None, seed=0, engine=None, **slice_options):
     """patients: [{'name', 'volume': path, 'groundtruth': path or None, 'skullmap': path or None}] -> slice cache in `directory`.
-    slice_options: volume_to_slices keywords.  Returns the index dict that was written."""
+    slice_options: volume_to_slices keywords; engine: volume_to_slices' device resampler.  Returns the index dict that was written."""
     from .slice_cache import SET_TYPES, write_cache
     split = partition_patients(len(patients), partition, np.random.default_rng(seed))
     set_of = {}
@@ -218,7 +229,7 @@ def build_cache(directory, patients, partition=None, seed=0, **slice_options):
         vol, _ = read_nifti(p['volume'])
         seg = read_nifti(p['groundtruth'])[0] if p.get('groundtruth') else None
         msk = read_nifti(p['skullmap'])[0] if p.get('skullmap') else None
-        im, lb, kept = volume_to_slices(vol, seg, msk, **slice_options)
+        im, lb, kept = volume_to_slices(vol, seg, msk, engine=engine, **slice_options)
         if len(kept):
             images.append(im); labels.append(lb); sets += [set_of[i]] * len(kept); owner += [p.get('name', str(i))] * len(kept)
     if not images:
