@@ -259,7 +259,11 @@ int uad_residual(const float* x, const float* xr, const float* mask, int n, int 
  * uad_scores_*: every threshold metric of trainers/Metrics.py from ONE descending device sort of the n voxel scores:
  *   AUROC (sklearn roc_curve + auc, Metrics.py:45-47), AUPRC (sklearn average_precision_score, :17-19) and
  *   dice(score > t, label) for batches of thresholds (the inner step of compute_dice_curve_recursive, :138-162).
- *   label: fp32, nonzero = positive.  create is synchronous (allocates; one 32-bit radix sort + scans). */
+ *   label: fp32, nonzero = positive.  create is synchronous (allocates; one 32-bit radix sort + scans).
+ *   Single-class labels give what the reference's numpy divisions give: no positive label -> AUROC = AUPRC = nan; no negative
+ *   label -> AUROC = nan, AUPRC = 1; dice with nothing predicted and nothing labelled -> nan (0/0).  Thresholds are the distinct
+ *   scores under numpy's `diff != 0`: -0.0 and +0.0 are one threshold, every +-inf score is one of its own (inf - inf is nan);
+ *   nan scores are undefined. */
 typedef struct uad_scores uad_scores_t;
 int uad_erode_cross(const float* mask, int n, int H, int W, int iterations, float* out, void* stream);
 int uad_median3d(const float* vol, int D, int H, int W, int ksize, float* out, void* stream);

@@ -9,6 +9,8 @@ import pytest
 import scipy.ndimage
 import torch
 
+from tests.scoring_cases import host_threshold
+
 pytestmark = pytest.mark.gpu
 
 try:
@@ -208,11 +210,6 @@ def test_detection_rate_random_pairs(eng, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------- threshold at precision
-def host_threshold(p, y, precision):
-    _, prec, _, thr = Metrics.compute_prc(np.asarray(p, np.float64), np.asarray(y).astype(bool))
-    return float(thr[np.argmax(prec <= precision)])
-
-
 @pytest.mark.parametrize('n,levels', [(1000, 17), (300000, 4096), (2000003, 0)])
 def test_threshold_at_precision_matches_host_formula(eng, n, levels):
     rng = np.random.default_rng(n)

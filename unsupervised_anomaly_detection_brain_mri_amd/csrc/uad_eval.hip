@@ -268,10 +268,13 @@ void launch_scan(const Tin* in, size_t n, Tout* out, Tout* bsum, Tout* total, hi
 }
 
 // ---- distinct-score positions (sklearn's thresholds): flag the last element of every run of equal scores, compact their indices ----
+// The reference's rule is `np.diff(score) != 0` on the sorted scores: -0.0 and +0.0 tie (their difference is 0), equal infinities do NOT
+// (inf - inf is nan, and nan != 0), so every +-inf score is a threshold of its own.  The host path (trainers/Metrics.py) reads the same.
+__device__ __forceinline__ bool closes_run(float a, float next) { return a != next || isinf(a); }
 __global__ void __launch_bounds__(256) distinct_flag_kernel(const float* __restrict__ score, unsigned char* __restrict__ flag, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    flag[i] = (i + 1 == n) || (score[i] != score[i + 1]);
+    flag[i] = (i + 1 == n) || closes_run(score[i], score[i + 1]);
 }
 __global__ void __launch_bounds__(256) compact_kernel(const unsigned char* __restrict__ flag, const unsigned* __restrict__ pos, unsigned* __restrict__ didx, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -289,8 +292,10 @@ __global__ void __launch_bounds__(1024) auc_ap_kernel(const unsigned* __restrict
         const double tps = (double)tp[i], fps = (double)(i + 1) - tps;
         double tps_p = 0.0, fps_p = 0.0;
         if (m > 0) { const unsigned j = didx[m - 1]; tps_p = (double)tp[j]; fps_p = (double)(j + 1) - tps_p; }
-        if (P > 0) ap += (tps - tps_p) / P * (tps / (tps + fps));
-        if (P > 0 && Nn > 0) auc += (fps - fps_p) / Nn * (tps + tps_p) / P * 0.5;
+        // single-class labels: no positives -> 0/0 in both sums, no negatives -> 0/0 in the AUROC sum.  The nan is the result, as in the
+        // reference's numpy divisions (and dice_at_kernel below); nd >= 1, so at least one term is added
+        ap += (tps - tps_p) / P * (tps / (tps + fps));
+        auc += (fps - fps_p) / Nn * (tps + tps_p) / P * 0.5;
     }
     s_ap[threadIdx.x] = ap;
     s_auc[threadIdx.x] = auc;
@@ -328,7 +333,7 @@ __global__ void __launch_bounds__(256) prec_threshold_kernel(const float* __rest
     __syncthreads();
     unsigned mine = 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
-        const bool last = (i + 1 == n) || (score[i] != score[i + 1]);
+        const bool last = (i + 1 == n) || closes_run(score[i], score[i + 1]);
         if (last && (double)tp[i] / (double)(i + 1) <= p) mine = (unsigned)(i + 1);        // i grows along the loop
     }
     if (mine) atomicMax(&s_best, mine);
