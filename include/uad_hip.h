@@ -341,6 +341,36 @@ size_t uad_zoom_spline3_workspace(int n, int h, int w, int boundary);
 int uad_zoom_spline3(const float* in, int n, int h, int w, int H, int W, int boundary, int out_kind, void* out, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- order statistics without a sort (csrc/uad_select.hip) ----------------------------------------------------
+ * uad_select_quantiles: segmented radix select over fp32 `in` [n_seg, n_per_seg] (device, contiguous).  For each segment: m = the number
+ *   of values that pass `filter` (UAD_SELECT_ALL | UAD_SELECT_NONNEG: v >= 0) -> m_out[seg] (int64), and for each of the k <=
+ *   UAD_SELECT_MAX_Q fractions q[j] (host doubles in [0, 1]) the two order statistics of the passing values that bracket the virtual index
+ *   v = (m - 1) * q[j] of numpy's 'linear' method -- lo = x_(floor v), hi = x_(min(floor v + 1, m - 1)) -> bracket_out[seg][2 j], [2 j + 1]
+ *   (fp32 [n_seg, 2 k]).  Both are values of the input, bit for bit: no arithmetic touches a value; the caller finishes the interpolation.
+ *   The index is ONE multiply on the device in the float type numpy forms it in: double, or -- bit j of f32_index_mask -- float32, which
+ *   is what np.percentile / np.quantile of a float32 array with a Python-scalar q do ((n - 1) * float32(q), next = float32(floor v) + 1).
+ *   This is np.percentile(v, 0 / 99.8) + max of utils/NII.py:50-66 in one call (q = {lower, upper, 1}), np.percentile(slice, 90) of
+ *   dataloaders/MSLUB.py:161 with one segment per slice, np.quantile(volume, 0.9) of utils/Evaluation.py:205, and, with UAD_SELECT_NONNEG,
+ *   np.percentile(var[var >= 0], 99.8) of utils/Evaluation.py:404-408.  m == 0: the brackets are NaN.
+ *   PRECONDITION: the input holds no NaN (the NIfTI reader zeroes them, utils/NII.py:12-16); a NaN is ordered by its bit pattern.  -0 and +0
+ *   compare equal as in numpy; +0 is returned for either.  +-inf are ordinary values.
+ *   Four passes over the 8-bit digits of the order-preserving key, most significant first, four launches, no host synchronisation, no
+ *   second copy of the data: 4 x 4 B x n of HBM reads.  Grid = (tiles of UAD_SELECT_TILE values per segment, segments).  Integer atomics only:
+ *   results are bit-reproducible and a segment's result does not depend on the other segments.
+ *   workspace: device memory of at least uad_select_workspace(n_seg) bytes, 16-byte aligned, owned by the caller, any contents, free for
+ *   reuse once the call's work on `stream` is done.  n_seg <= 65535, n_per_seg <= 2^31 - 1.
+ * uad_histogram_edges: counts[i] (int64 [bins], device) = the number of values with edges[i] <= v < edges[i + 1], the last bin closed
+ *   (v <= edges[bins]); values outside [edges[0], edges[bins]] and NaNs are dropped.  edges: bins + 1 fp32 on the device, non-decreasing, bins <=
+ *   UAD_HISTOGRAM_MAX_BINS.  With the table np.histogram_bin_edges gives this is np.histogram (utils/Evaluation.py:404-408: 50 bins).
+ * uad_clamp_scale: out[i] = (v < lo ? lo : v > hi ? hi : v) * scale, the clamp-and-scale tail of utils/NII.py:57-66; out may alias in. */
+enum { UAD_SELECT_ALL = 0, UAD_SELECT_NONNEG = 1 };
+enum { UAD_SELECT_MAX_Q = 4, UAD_SELECT_TILE = 8192, UAD_HISTOGRAM_MAX_BINS = 1024 };
+size_t uad_select_workspace(int n_seg);
+int uad_select_quantiles(const float* in, int n_seg, long long n_per_seg, const double* q, int k, unsigned f32_index_mask, int filter,
+                         long long* m_out, float* bracket_out, void* workspace, size_t workspace_bytes, void* stream);
+int uad_histogram_edges(const float* in, long long n, const float* edges, int bins, long long* counts, void* stream);
+int uad_clamp_scale(const float* in, long long n, float lo, float hi, float scale, float* out, void* stream);
+
 /* ---- f-AnoGAN (unified graph) ------------------------------------------------------------------------------
  * Replaces models/fanogan.py:11-84 (encoder + generator + critic graph) and the three optimisation phases of
  * trainers/fAnoGAN.py:45-77 (losses :50-66, the WGAN-GP penalty's tf.gradients :55-57, three Adams :71-77);

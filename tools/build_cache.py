@@ -4,7 +4,8 @@
     python tools/build_cache.py <root> <cache_dir> --protocol FLAIR --res 128 --start 15 --end 125
 
 The volume -> slice steps are those of utils/nifti.py (skull stripping, percentile scaling, empty-slice filter, pad / zoom); the ITK
-CurvatureFlow denoising of the reference loaders is not applied.  --device-resample runs the pad / zoom step's cubic spline on the GPU.
+CurvatureFlow denoising of the reference loaders is not applied.  --device-resample runs the pad / zoom step's cubic spline on the GPU;
+--device-stats also runs the percentile scaling and the empty-slice filter there (one upload per volume, resampled slices come back).
 """
 import argparse
 import json
@@ -26,6 +27,8 @@ def main():
     ap.add_argument('--train', type=float, default=0.7); ap.add_argument('--val', type=float, default=0.2); ap.add_argument('--test', type=float, default=0.1)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device-resample', action='store_true', help='resample the slices with the device spline op (uad_zoom_spline3) instead of scipy')
+    ap.add_argument('--device-stats', action='store_true',
+                    help='percentile scaling and empty-slice filter on the device select op (uad_select_quantiles); implies --device-resample')
     a = ap.parse_args()
     patients = []
     for name in sorted(os.listdir(a.root)):
@@ -38,11 +41,11 @@ def main():
     if not patients:
         raise SystemExit(f'no <patient>/<patient>_{a.protocol}.nii.gz under {a.root}')
     engine = None
-    if a.device_resample:
+    if a.device_resample or a.device_stats:
         from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
         engine = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)       # any handle carries the model-independent device ops
     info = nifti.build_cache(a.cache, patients, partition={'TRAIN': a.train, 'VAL': a.val, 'TEST': a.test}, seed=a.seed, engine=engine, axis=a.axis,
-                             slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res))
+                             slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'device_stats': a.device_stats} if engine is not None else {}))
     print(json.dumps(info))
 
 

@@ -1,0 +1,137 @@
+"""Host numpy against the device order statistics (uad_select_quantiles, uad_histogram_edges, uad_clamp_scale) on the three places the
+volume -> slice path and the evaluation tail take order statistics of large arrays.
+
+    python tools/select_bench.py [--out profiles/r09_select.json] [--host-reps 3] [--reps 20]
+
+Cases:
+  ingest       one 110 x 217 x 181 skull-stripped volume: normalize_scaling (np.percentile 0 / 99.8 + max, clamp, scale) and the
+               empty-slice filter (np.percentile(slice, 90) per slice) -- on the device one select call, one clamp-and-scale pass and one
+               segmented select with a segment per slice;
+  prior        np.quantile(volume, 0.9) of the same volume (utils/Evaluation.py:205);
+  mc_tail      np.percentile(var[var >= 0], 99.8) + the 50-bin np.histogram of 21.6 M variances (utils/Evaluation.py:404-408).
+For each: `host` = numpy on this machine's CPU (host clock); `device` = the engine ops on a host array, upload and the small downloads
+included (host clock around calls that end in a synchronising download); `device_resident` = the same ops on a device-resident tensor;
+`sort` = the library's own radix sort of the same array for comparison (engine.scores: uad_scores_create -- the four-pass sort with its
+label byte, the prefix sums and the AUC kernel behind it; it is the only entry that sorts).  Every timed shape is warmed up first; median / min / max over the repetitions.  Each device result is also compared
+with numpy's (`equal`).  The bound reported is the select's HBM read traffic, 4 passes x 4 B x n.  Needs the GPU: there is no fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.utils import nifti  # noqa: E402
+
+S, NH, NW = 110, 217, 181
+N_TAIL = 21_600_000
+
+
+def stats(ms):
+    return {'median_ms': statistics.median(ms), 'min_ms': min(ms), 'max_ms': max(ms), 'reps': len(ms)}
+
+
+def timed(fn, reps, warmup, sync=None):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        if sync:
+            sync()
+        t0 = time.perf_counter()
+        fn()
+        if sync:
+            sync()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return stats(out)
+
+
+def volume(seed=0):
+    """A skull-stripped volume: an ellipsoid of smooth tissue plus noise, exact zeros outside -- about half of the voxels."""
+    rng = np.random.default_rng(seed)
+    z, y, x = np.meshgrid(np.linspace(-1, 1, S), np.linspace(-1, 1, NH), np.linspace(-1, 1, NW), indexing='ij', sparse=True)
+    r = np.sqrt((z / 0.9) ** 2 + (y / 0.85) ** 2 + (x / 0.8) ** 2)
+    v = (600.0 * np.clip(1.15 - r, 0, None) + 40.0 * rng.standard_normal((S, NH, NW))) * (r < 1.0)
+    return np.ascontiguousarray(v.astype(np.float32))
+
+
+def host_ingest(v):
+    n = nifti.normalize_scaling(v)
+    return n, [s for s in range(S) if not np.percentile(n[s], 90) < 0.2]
+
+
+def device_ingest(eng, v):
+    d = nifti._normalize_scaling_on(eng, eng._dev(v), 0, 99.8)
+    stat = eng.percentile(d, 90, segments=S)
+    return d, [int(i) for i in np.flatnonzero(~(stat < 0.2))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--host-reps', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=20)
+    a = ap.parse_args()
+    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    sync = lambda: torch.cuda.synchronize(eng.device)
+    res = {'device': torch.cuda.get_device_name(eng.device), 'numpy': np.__version__, 'cases': {}}
+
+    v = volume()
+    vd = eng._dev(v)
+    n = v.size
+    hn, hk = host_ingest(v)
+    dn, dk = device_ingest(eng, v)
+    res['cases']['ingest'] = {
+        'voxels': n, 'equal': bool(hk == dk and dn.cpu().numpy().tobytes() == hn.tobytes()), 'kept_slices': len(hk),
+        'host': timed(lambda: host_ingest(v), a.host_reps, 1),
+        'device': timed(lambda: device_ingest(eng, v), a.reps, 2, sync),
+        'device_resident': timed(lambda: device_ingest(eng, vd), a.reps, 2, sync),
+        'select_only_resident': timed(lambda: eng.select_quantiles(vd, [0.0, 0.998, 1.0], [True, True, False]), a.reps, 2, sync),
+        'sort': timed(lambda: eng.scores(vd.reshape(-1), vd.reshape(-1)).close(), a.reps, 2, sync),
+        'select_read_bound_bytes': 2 * 4 * 4 * n}                 # two select calls: the volume, then one segment per slice
+
+    res['cases']['prior'] = {
+        'voxels': n, 'equal': bool(eng.quantile(vd, 0.9) == np.quantile(v, 0.9)),
+        'host': timed(lambda: np.quantile(v, 0.9), a.host_reps, 1),
+        'device': timed(lambda: eng.quantile(v, 0.9), a.reps, 2, sync),
+        'device_resident': timed(lambda: eng.quantile(vd, 0.9), a.reps, 2, sync),
+        'sort': res['cases']['ingest']['sort'],
+        'select_read_bound_bytes': 4 * 4 * n}
+
+    rng = np.random.default_rng(1)
+    var = (rng.random(N_TAIL, dtype=np.float32) ** 4 * np.float32(3e-3)).astype(np.float32)
+    var[::2] = 0.0                                                 # outside the eroded brain mask the variance is exactly zero
+    vard = eng._dev(var)
+
+    def host_tail():
+        hi = float(np.percentile(var[var >= 0], 99.8))
+        return hi, np.histogram(var, bins=50, range=(1e-5, hi))[0]
+
+    def device_tail(x):
+        hi = float(eng.percentile(x, 99.8, nonneg_only=True))
+        return hi, eng.histogram(x, 50, (1e-5, hi))[0]
+    h, d = host_tail(), device_tail(vard)
+    res['cases']['mc_tail'] = {
+        'values': N_TAIL, 'equal': bool(h[0] == d[0] and np.array_equal(h[1], d[1])),
+        'host': timed(host_tail, a.host_reps, 1),
+        'device': timed(lambda: device_tail(var), max(a.reps // 4, 3), 1, sync),
+        'device_resident': timed(lambda: device_tail(vard), a.reps, 2, sync),
+        'sort': timed(lambda: eng.scores(vard, vard).close(), max(a.reps // 4, 3), 1, sync),
+        'select_read_bound_bytes': 4 * 4 * N_TAIL}
+    eng.close()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, 'w') as f:
+            f.write(json.dumps(res, indent=1) + '\n')
+
+
+if __name__ == '__main__':
+    main()

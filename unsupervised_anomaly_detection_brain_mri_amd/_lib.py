@@ -54,6 +54,8 @@ class UadGanIO(C.Structure):
 
 ZOOM_CONSTANT, ZOOM_NEAREST = 0, 1
 ZOOM_F32, ZOOM_I32 = 0, 1
+SELECT_ALL, SELECT_NONNEG = 0, 1
+SELECT_MAX_Q, SELECT_TILE, HISTOGRAM_MAX_BINS = 4, 8192, 1024      # include/uad_hip.h: UAD_SELECT_MAX_Q, UAD_SELECT_TILE, UAD_HISTOGRAM_MAX_BINS
 GAN_ENCODER, GAN_GENERATOR, GAN_DISCRIMINATOR = 0, 1, 2
 GAN_UNIFIED, GAN_RESNET, GAN_ANOVAEGAN, GAN_AAE = 0, 1, 2, 3
 GAN_GROUP_VAE = 3
@@ -128,6 +130,11 @@ SYMBOLS = {
     'uad_zoom_spline3_workspace': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'uad_zoom_spline3': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]),
+    'uad_select_workspace': (C.c_size_t, [C.c_int]),
+    'uad_select_quantiles': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.c_int, C.c_uint, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    'uad_histogram_edges': (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_clamp_scale': (C.c_int, [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     'uad_rng_fill': (C.c_int, [C.POINTER(UadRngJob), C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_void_p]),
     'uad_clock_probe': (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_void_p]),
     'uad_gan_create': (C.c_int, [C.POINTER(UadGanConfig), C.POINTER(C.c_void_p)]),

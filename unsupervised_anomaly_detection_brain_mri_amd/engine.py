@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .utils.order_stats import OrderStatOps, as_float32_exact
 
 
 class _DevArray:
@@ -73,9 +74,10 @@ def zoom_output_hw(in_hw, factors):
     return tuple(int(round(i * z)) for i, z in zip(in_hw, f))
 
 
-class _EvalOps:
-    """Model-independent device ops of the evaluation path (erosion, 3-D median, residual maps, sort-based metrics); shared by
-    the AE-family Engine and the f-AnoGAN GanEngine.  Needs self.lib, self.device, self._dev, self._stream."""
+class _EvalOps(OrderStatOps):
+    """Model-independent device ops of the evaluation path (erosion, 3-D median, residual maps, sort-based metrics, order statistics); shared
+    by the AE-family Engine and the f-AnoGAN GanEngine.  Needs self.lib, self.device, self._dev, self._stream.
+    quantile / percentile / histogram come from utils.order_stats.OrderStatOps over the raw ops select_quantiles / histogram_edges below."""
 
     # ---------------------------------------------------------------- scoring (SURVEY.md §8 row a14)
     def erode_cross(self, masks, iterations=12):
@@ -173,6 +175,63 @@ class _EvalOps:
                                                self._stream()))
         tps, fps, fns = (int(c) for c in counts.cpu().tolist())
         return tps, fps, fns
+
+    # ---------------------------------------------------------------- order statistics (csrc/uad_select.hip)
+    def _f32_exact(self, values):
+        """-> contiguous fp32 device tensor of a float32 / float64 array or tensor; ValueError when a float64 value is not a float32 number."""
+        if isinstance(values, torch.Tensor):
+            if values.dtype == torch.float64:
+                f = values.to(torch.float32)
+                if not bool((f.to(torch.float64) == values).all()):
+                    raise ValueError('float64 values that float32 cannot represent: the device order statistics would not equal numpy')
+                values = f
+            elif values.dtype != torch.float32:
+                raise TypeError(f'order statistics take float32 or float64 values, got {values.dtype}')
+            return values.to(self.device).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(as_float32_exact(values))).to(self.device)
+
+    def select_workspace(self, segments=1):
+        """A workspace tensor for select_quantiles calls of up to `segments` segments (any contents; the call initialises it)."""
+        nbytes = int(self.lib.uad_select_workspace(int(segments)))
+        return torch.empty(max(nbytes // 8, 1), device=self.device, dtype=torch.int64)
+
+    def select_quantiles(self, values, fractions, f32_index, segments=None, nonneg_only=False, workspace=None):
+        """uad_select_quantiles: per segment (row of values.reshape(segments, -1); None = the whole array) the count m of values that pass
+        the filter and, for each fraction q, the order statistics x_(floor v), x_(min(floor v + 1, m - 1)) around v = (m - 1) * q, formed in
+        float32 where f32_index[j] (numpy's index type for a float32 fraction) and in float64 otherwise.
+        -> (m [n_seg] int64, lo [n_seg,k] float32, hi [n_seg,k] float32) on the host; NaN brackets where m == 0.  NaN-free input."""
+        t = self._f32_exact(values)
+        n_seg = 1 if segments is None else int(segments)
+        k = len(fractions)
+        if n_seg < 1 or t.numel() == 0 or t.numel() % n_seg:
+            raise ValueError(f'{t.numel()} values do not split into {n_seg} non-empty segments')
+        if not 1 <= k <= _lib.SELECT_MAX_Q or len(f32_index) != k:
+            raise ValueError(f'1 .. {_lib.SELECT_MAX_Q} fractions with one index type each, got {k} / {len(f32_index)}')
+        ws = workspace if workspace is not None else self.select_workspace(n_seg)
+        m = torch.empty(n_seg, device=self.device, dtype=torch.int64)
+        br = torch.empty((n_seg, 2 * k), device=self.device, dtype=torch.float32)
+        q = (C.c_double * k)(*[float(v) for v in fractions])
+        mask = sum(1 << j for j, f in enumerate(f32_index) if f)
+        _lib.check(self.lib.uad_select_quantiles(_ptr(t), n_seg, t.numel() // n_seg, q, k, mask, _lib.SELECT_NONNEG if nonneg_only else _lib.SELECT_ALL,
+                                                 _ptr(m), _ptr(br), _ptr(ws), ws.numel() * ws.element_size(), self._stream()))
+        br = br.cpu().numpy()
+        return m.cpu().numpy(), br[:, 0::2], br[:, 1::2]
+
+    def histogram_edges(self, values, edges32):
+        """uad_histogram_edges: counts [bins] (numpy int64) of edges32[i] <= v < edges32[i + 1], last bin closed, outside values dropped."""
+        t = self._f32_exact(values)
+        e = torch.from_numpy(np.ascontiguousarray(edges32, np.float32)).to(self.device)
+        counts = torch.empty(e.numel() - 1, device=self.device, dtype=torch.int64)
+        _lib.check(self.lib.uad_histogram_edges(_ptr(t), t.numel(), _ptr(e), e.numel() - 1, _ptr(counts), self._stream()))
+        return counts.cpu().numpy()
+
+    def clamp_scale(self, values, lo=None, hi=None, scale=1.0, out=None):
+        """uad_clamp_scale: (v < lo ? lo : v > hi ? hi : v) * scale elementwise in fp32 -> device tensor of values' shape (out may be values)."""
+        t = self._dev(values)
+        out = torch.empty_like(t) if out is None else out
+        _lib.check(self.lib.uad_clamp_scale(_ptr(t), t.numel(), -math.inf if lo is None else float(lo), math.inf if hi is None else float(hi),
+                                            float(scale), _ptr(out), self._stream()))
+        return out
 
     def scores(self, predictions, labels):
         """One descending device sort of all voxel scores -> Scores object (AUROC, AUPRC, dice at thresholds)."""

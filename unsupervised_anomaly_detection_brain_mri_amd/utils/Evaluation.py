@@ -303,10 +303,18 @@ def _score_diffs(model, diffs, labels, options, variances=None):
     if variances:
         # utils/Evaluation.py:404-408: histogram of the epistemic variances (50 bins, 1e-5 .. their 99.8th percentile)
         ev['epistemic_variance'] = np.concatenate(variances, axis=0)
-        pos = ev['epistemic_variance'][ev['epistemic_variance'] >= 0]
-        hi = float(np.percentile(pos, 99.8))
+        eng = model.engine
+        percentile, histogram = getattr(eng, 'percentile', None), getattr(eng, 'histogram', None)
+        if percentile is not None and histogram is not None:
+            # device select over the non-negative variances and the edge-table histogram (uad_select_quantiles, uad_histogram_edges): numpy's numbers
+            hi = float(percentile(ev['epistemic_variance'], 99.8, nonneg_only=True))
+            hist = lambda: histogram(ev['epistemic_variance'], 50, (1e-5, hi))[0]
+        else:                                        # host stand-in engine: the host statement
+            pos = ev['epistemic_variance'][ev['epistemic_variance'] >= 0]
+            hi = float(np.percentile(pos, 99.8))
+            hist = lambda: np.histogram(ev['epistemic_variance'], bins=50, range=(1e-5, hi))[0]
         # (the reference's np.histogram raises when every variance is below 1e-5; an empty histogram is returned here instead)
-        ev['uncertaintyHistogram'] = (np.histogram(ev['epistemic_variance'], bins=50, range=(1e-5, hi))[0] if hi > 1e-5 else np.zeros(50, np.int64)).tolist()
+        ev['uncertaintyHistogram'] = (hist() if hi > 1e-5 else np.zeros(50, np.int64)).tolist()
     return ev
 
 
@@ -321,16 +329,29 @@ def _zoom_output_hw(shape, zf):
     return tuple(int(round(i * z)) for i, z in zip(shape, zf))          # scipy.ndimage.zoom's output shape
 
 
+def _prior_quantile(data, engine):
+    """np.quantile(data, 0.9) (utils/Evaluation.py:205); through the device select (engine._EvalOps.quantile) when the engine has it and
+    the volume's values are float32 numbers -- the op returns numpy's value and dtype.  Other data keep the host statement."""
+    quantile = getattr(engine, 'quantile', None)
+    if quantile is not None:
+        try:
+            return quantile(data, 0.9)
+        except (TypeError, ValueError):      # not float32-representable (a scaled float64 volume), or not a float array: the host statement
+            pass
+    return np.quantile(data, 0.9)
+
+
 def collect_patient_volume(datasetObj, patient, nii_filename, options, engine=None):
     """utils/Evaluation.py:205-232: load the volume, its ground truth and skull map; take slices sliceStart .. min(sliceEnd, #slices) along
     options.axis; zoom every slice to options.sliceResolution -- cubic spline for the image (scipy.ndimage.zoom default order 3), the same
     call with mode='nearest' for the integer label / skull maps, exactly as written there.  Returns (x [S,H,W] float64, seg [S,H,W] int,
     skullmap [S,H,W] int, prior_quantile of the whole loaded volume, slice indices) or None when the volume is too thin (:210-211).
     engine: an engine with the device `zoom` op (engine._EvalOps.zoom) -- the three maps of the patient are stacked and resampled in three
-    batched device calls (image: 'constant', fp32; label / skull: 'nearest', int32) and downloaded; None = the host loop above."""
+    batched device calls (image: 'constant', fp32; label / skull: 'nearest', int32) and downloaded; None = the host loop above.  With an
+    engine that has the device order statistics the prior quantile is one select call (_prior_quantile)."""
     o = datasetObj.options
     nii, nii_seg, nii_skullmap = datasetObj.load_volume_and_groundtruth(nii_filename, patient)
-    prior_quantile = np.quantile(nii.data, 0.9)
+    prior_quantile = _prior_quantile(nii.data, engine)
     if min(nii.shape()) < (o.sliceEnd - o.sliceStart):
         return None
     slice_start = o.sliceStart if o.sliceStart else 0

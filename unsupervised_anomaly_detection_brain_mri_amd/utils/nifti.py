@@ -124,8 +124,43 @@ def read_nrrd(path):
     return np.frombuffer(body, dt, cnt).reshape(sizes, order='F'), hdr
 
 
-def normalize_scaling(vol, lower=0, upper=99.8):
-    """NII.normalize(method='scaling', lowerpercentile, upperpercentile) (NII.py:50-66)."""
+def _has_order_stats(engine):
+    return engine is not None and all(hasattr(engine, op) for op in ('select_quantiles', 'clamp_scale', 'percentile'))
+
+
+def _normalize_scaling_on(engine, v, lower, upper):
+    """normalize_scaling of an fp32 array resident with `engine` (engine._dev), without a sort and without leaving the engine: ONE select call
+    brackets the lower percentile, the upper percentile and the maximum (q = {lower, upper, 1}).  Clamping is monotone, so the order
+    statistics of the lower-clamped array are the clamped order statistics: the upper percentile is interpolated from the clamped brackets,
+    exactly what np.percentile returns after `v[v < q] = q`.  Then one clamp-and-scale pass.  NaN-free input."""
+    from .order_stats import finish_linear, percentile_fractions
+    f32 = np.dtype(np.float32)
+    ql = percentile_fractions(0 if lower is None else lower, f32)
+    qu = percentile_fractions(100 if upper is None else upper, f32)
+    m, lo, hi = engine.select_quantiles(v, [float(ql), float(qu), 1.0], [ql.dtype == np.float32, qu.dtype == np.float32, False])
+    clamp_lo = clamp_hi = None
+    top = np.float32(hi[0, 2])                                              # v.max()
+    if lower is not None:
+        clamp_lo = finish_linear(m, lo[:, 0], hi[:, 0], ql, f32)[0]
+        lo, hi = np.where(lo < clamp_lo, clamp_lo, lo), np.where(hi < clamp_lo, clamp_lo, hi)
+        top = clamp_lo if top < clamp_lo else top
+    if upper is not None:
+        clamp_hi = finish_linear(m, lo[:, 1], hi[:, 1], qu, f32)[0]
+        top = clamp_hi if top > clamp_hi else top
+    scale = np.float32(1.0 / top) if top > 0.0 else np.float32(1.0)
+    return engine.clamp_scale(v, clamp_lo, clamp_hi, scale)
+
+
+def normalize_scaling(vol, lower=0, upper=99.8, engine=None):
+    """NII.normalize(method='scaling', lowerpercentile, upperpercentile) (NII.py:50-66).
+    engine: an engine with the device order statistics (engine._EvalOps.select_quantiles / clamp_scale): both percentiles and the maximum
+    come from one device select call and the clamp-and-scale is one device pass; the same float32 array comes back.  The device path takes
+    Python-scalar percentiles and NaN-free input (volume_to_slices zeroes NaNs first); an engine without the ops gets the host statement.
+    Bit-equal to the host statement except for the SIGN of a zero that a zero-valued lower percentile clamps negative values to: numpy's
+    comes out of its partition order, the op knows one zero (+0).  With lower = 0, the pipeline's setting, nothing is clamped from below."""
+    if _has_order_stats(engine) and all(p is None or isinstance(p, (int, float)) for p in (lower, upper)):
+        out = _normalize_scaling_on(engine, engine._dev(np.ascontiguousarray(vol, np.float32)), lower, upper)
+        return out.cpu().numpy().reshape(np.shape(vol))
     v = vol.astype(np.float32)
     if lower is not None:
         q = np.percentile(v, lower); v[v < q] = q
@@ -144,12 +179,17 @@ def crop_center(img, cropx, cropy):
 
 
 def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0, slice_end=155, slice_resolution=None, skull_stripping=True,
-                     view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None):
+                     view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None,
+                     device_stats=None):
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
     map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
     engine: an engine with the device `zoom` op (engine._EvalOps.zoom): the kept, padded slices are resampled in one batched device call each
-    for the image ('constant') and the label map ('nearest', fp32, then >= 0.9) instead of two scipy calls per slice."""
+    for the image ('constant') and the label map ('nearest', fp32, then >= 0.9) instead of two scipy calls per slice.
+    device_stats (default: on when `engine` has the order-statistic ops, engine._EvalOps.select_quantiles): the masked volume is moved to
+    slice-major order and uploaded ONCE as fp32, normalised there (_normalize_scaling_on), the empty-slice filter is one segmented select with
+    one segment per slice, and the kept slices are padded and resampled from the device-resident volume -- no second upload of the image.
+    The label path is unchanged.  Same kept slices and the same bits as device_stats=False."""
     from scipy.ndimage import rotate, zoom
     if denoise:
         raise NotImplementedError("nii.denoise() is SimpleITK's CurvatureFlow filter (MSLUB.py:257); it is not restated here")
@@ -162,13 +202,27 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     seg = (np.asarray(seg) >= 0.9).astype(np.float64)                       # MSLUB.py:264-265
     if skull_stripping and brainmask is not None:
         vol = vol * (np.asarray(brainmask) >= 0.1)                          # NII.apply_skullmap
-    vol = normalize_scaling(vol)
+    if device_stats is None:
+        device_stats = _has_order_stats(engine)
+    elif device_stats and not _has_order_stats(engine):
+        raise ValueError('device_stats needs an engine with the order-statistic ops (select_quantiles, clamp_scale)')
+    vol_dev = keep_dev = None
+    if device_stats:
+        vol_dev = _normalize_scaling_on(engine, engine._dev(np.ascontiguousarray(np.moveaxis(vol, ax, 0), np.float32)), 0, 99.8)
+        s_end = min(slice_end, vol.shape[ax])
+        if s_end > slice_start:
+            stat = engine.percentile(vol_dev[slice_start:s_end], empty_percentile, segments=s_end - slice_start)
+            keep_dev = [slice_start + int(i) for i in np.flatnonzero(~(stat < empty_thresh))]      # MSLUB.py:161, one segment per slice
+        else:
+            keep_dev = []
+    else:
+        vol = normalize_scaling(vol)
     sds, sss, kept_s = [], [], []
-    for s in range(slice_start, min(slice_end, vol.shape[ax])):
+    for s in (keep_dev if device_stats else range(slice_start, min(slice_end, vol.shape[ax]))):
         idx = [slice(None)] * 3
         idx[ax] = s
-        sd, ss = vol[tuple(idx)], seg[tuple(idx)]
-        if np.percentile(sd, empty_percentile) < empty_thresh:              # MSLUB.py:161: skip "empty" slices
+        sd, ss = vol[tuple(idx)], seg[tuple(idx)]               # (device_stats: sd only lends its shape; the image stays on the device)
+        if not device_stats and np.percentile(sd, empty_percentile) < empty_thresh:              # MSLUB.py:161: skip "empty" slices
             continue
         if slice_resolution is not None:
             H, W = slice_resolution
@@ -182,11 +236,24 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
                 ss = zoom(ss, f, mode='nearest')
                 ss = (ss >= 0.9).astype(np.float64)
         sds.append(sd); sss.append(ss); kept_s.append(s)
-    if engine is not None and slice_resolution is not None and sds:
+    if device_stats and sds:
+        # the kept slices, gathered and zero-padded where they are: rows of the slice-major device volume into the padded batch
+        kept_dev = vol_dev[keep_dev]
+        hp, wp = sds[0].shape
+        h, w = kept_dev.shape[1:]
+        if (hp, wp) != (h, w):
+            y0, x0 = math.floor((hp - h) / 2.0) if h < hp else 0, math.floor((wp - w) / 2.0) if w < wp else 0
+            padded = kept_dev.new_zeros((kept_dev.shape[0], hp, wp))
+            padded[:, y0:y0 + h, x0:x0 + w] = kept_dev
+            kept_dev = padded
+        sds = kept_dev
+    if engine is not None and slice_resolution is not None and len(sds):
         f = float(slice_resolution[0]) / float(sds[0].shape[0])
         hw = tuple(int(round(i * f)) for i in sds[0].shape)                 # scipy.ndimage.zoom's output shape
-        sds = list(engine.zoom(np.stack(sds), hw, mode='constant').cpu().numpy())
+        sds = list(engine.zoom(sds if device_stats else np.stack(sds), hw, mode='constant').cpu().numpy())
         sss = list((engine.zoom(np.stack(sss), hw, mode='nearest').cpu().numpy().astype(np.float64) >= 0.9).astype(np.float64))
+    elif device_stats and len(sds):
+        sds = list(sds.cpu().numpy())
     imgs, labs, kept = [], [], []
     for sd, ss, s in zip(sds, sss, kept_s):
         for angle in rotations:
@@ -215,7 +282,8 @@ def partition_patients(n_patients, partition=None, rng=None):
 
 def build_cache(directory, patients, partition=None, seed=0, engine=None, **slice_options):
     """patients: [{'name', 'volume': path, 'groundtruth': path or None, 'skullmap': path or None}] -> slice cache in `directory`.
-    slice_options: volume_to_slices keywords; engine: volume_to_slices' device resampler.  Returns the index dict that was written."""
+    slice_options: volume_to_slices keywords (device_stats among them); engine: volume_to_slices' device resampler / order statistics.
+    Returns the index dict that was written."""
     from .slice_cache import SET_TYPES, write_cache
     split = partition_patients(len(patients), partition, np.random.default_rng(seed))
     set_of = {}
