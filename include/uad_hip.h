@@ -341,6 +341,25 @@ size_t uad_zoom_spline3_workspace(int n, int h, int w, int boundary);
 int uad_zoom_spline3(const float* in, int n, int h, int w, int H, int W, int boundary, int out_kind, void* out, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- cubic-spline affine transforms: the rotation augmentation (dataloaders/BRAINWEB.py:156-162, MSLUB.py / MSISBI2015.py alike) ----
+ * uad_affine_spline3: scipy.ndimage.affine_transform(a, M, offset, output_shape=(H,W), order=3, mode=..., prefilter=True) of every [h,w]
+ *   slice of an fp32 [n,h,w] batch under K transforms that share one prefilter -> [n,K,H,W].  xf: HOST array of K x 6 doubles
+ *   (m00 m01 m10 m11 off0 off1), 1 <= K <= UAD_AFFINE_MAX_K, all finite; output pixel (Y,X) reads the input coordinate
+ *   ((Y m00 + X m01) + off0, (Y m10 + X m11) + off1) in fp64 without fused multiply-adds -- scipy's order, so its coordinates bit for bit.
+ *   scipy.ndimage.rotate(a, angle, reshape=False) (the reference's call, once per slice and angle, and again with mode='nearest' for the
+ *   label map) is this with M = [[c, s], [-s, c]], c / s = cosdg / sindg(angle) and offset = (shape-1)/2 - M @ (shape-1)/2.
+ *   boundary UAD_ZOOM_CONSTANT = mode 'constant', cval 0: mirror prefilter, no padding; a pixel whose coordinate lies outside [0, h-1] x
+ *   [0, w-1] is 0, otherwise taps that step over the edge are mirror-folded.  UAD_ZOOM_NEAREST = mode 'nearest': every line is extended by
+ *   12 edge-replicated samples a side and filtered with scipy's REFLECT initial values (unlike uad_zoom_spline3, whose coordinates never
+ *   reach the outer padding); the coordinate moves by 12 and is not clamped, the four tap INDICES are clamped to the padded line.
+ *   out_kind as uad_zoom_spline3 (fp32, or int32 rounded half away from zero).  Transform k of a K-call has the bits of the K = 1 call, and a
+ *   slice's bits do not depend on n (no atomics).  h, w >= 2.  workspace: device memory of at least uad_affine_spline3_workspace(n, h, w,
+ *   boundary) bytes (the fp64 coefficient planes), 16-byte aligned, owned by the caller, free once the call's work on `stream` is done. */
+enum { UAD_AFFINE_MAX_K = 16 };
+size_t uad_affine_spline3_workspace(int n, int h, int w, int boundary);
+int uad_affine_spline3(const float* in, int n, int h, int w, int H, int W, const double* xf, int K, int boundary, int out_kind, void* out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- order statistics without a sort (csrc/uad_select.hip) ----------------------------------------------------
  * uad_select_quantiles: segmented radix select over fp32 `in` [n_seg, n_per_seg] (device, contiguous).  For each segment: m = the number
  *   of values that pass `filter` (UAD_SELECT_ALL | UAD_SELECT_NONNEG: v >= 0) -> m_out[seg] (int64), and for each of the k <=

@@ -6,6 +6,8 @@
 The volume -> slice steps are those of utils/nifti.py (skull stripping, percentile scaling, empty-slice filter, pad / zoom); the ITK
 CurvatureFlow denoising of the reference loaders is not applied.  --device-resample runs the pad / zoom step's cubic spline on the GPU;
 --device-stats also runs the percentile scaling and the empty-slice filter there (one upload per volume, resampled slices come back).
+--rotations A [A ...]: the rotation augmentation of the reference's dataset classes (dataloaders/BRAINWEB.py:156-162), one cached slice per
+angle; with a device engine the rotations run there too (uad_affine_spline3).  The default, 0, caches the unrotated slices only.
 """
 import argparse
 import json
@@ -29,6 +31,8 @@ def main():
     ap.add_argument('--device-resample', action='store_true', help='resample the slices with the device spline op (uad_zoom_spline3) instead of scipy')
     ap.add_argument('--device-stats', action='store_true',
                     help='percentile scaling and empty-slice filter on the device select op (uad_select_quantiles); implies --device-resample')
+    ap.add_argument('--rotations', type=float, nargs='+', default=[0], metavar='A',
+                    help='angles in degrees, one cached slice per angle and kept slice (0 = unrotated; on the device when an engine is used)')
     a = ap.parse_args()
     patients = []
     for name in sorted(os.listdir(a.root)):
@@ -45,7 +49,8 @@ def main():
         from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
         engine = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)       # any handle carries the model-independent device ops
     info = nifti.build_cache(a.cache, patients, partition={'TRAIN': a.train, 'VAL': a.val, 'TEST': a.test}, seed=a.seed, engine=engine, axis=a.axis,
-                             slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'device_stats': a.device_stats} if engine is not None else {}))
+                             slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'rotations': tuple(a.rotations)} if list(a.rotations) != [0] else {}),
+                             **({'device_stats': a.device_stats} if engine is not None else {}))
     print(json.dumps(info))
 
 

@@ -1,0 +1,101 @@
+"""Host scipy against the device cubic-spline rotation (uad_affine_spline3) on the rotation augmentation of the slice ingestion.
+
+    python tools/rotate_bench.py [--out profiles/r10_rotate.json] [--host-reps 3] [--reps 20]
+
+Workload: 110 resampled slices of 128 x 128 with rotations (-10, 0, 10) (dataloaders/BRAINWEB.py:156-162) -- the image ('constant') and the
+label map ('nearest', fp32), one output per slice and angle, angle 0 passing through.
+  host             scipy.ndimage.rotate(reshape=False), two calls per slice and non-zero angle as the reference's loop makes them; host clock.
+  device           engine.rotate on host arrays, results downloaded to host arrays: H2D + prefilter + gather per call + D2H; host clock around
+                   calls that end in the download (which synchronises).
+  device_resident  the same two calls on device-resident batches (what nifti.volume_to_slices does after engine.zoom), ending in one download
+                   of the rotated images and labels; host clock.
+The method is tools/resample_bench.py's: every timed shape is warmed up first; median / min / max over the repetitions are reported.  No
+threshold is set here.  Needs the GPU: there is no fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import scipy.ndimage
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.utils.synthetic import synthetic_slices  # noqa: E402
+
+S, R = 110, 128
+ROTATIONS = (-10, 0, 10)
+ANGLES = tuple(a for a in ROTATIONS if a != 0)
+
+
+def stats(ms):
+    return {'median_ms': statistics.median(ms), 'min_ms': min(ms), 'max_ms': max(ms), 'reps': len(ms)}
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def host_rotate(x, lab):
+    for k in range(S):
+        for a in ANGLES:
+            scipy.ndimage.rotate(x[k], a, reshape=False)
+            scipy.ndimage.rotate(lab[k], a, reshape=False, mode='nearest')
+
+
+def device_rotate(eng, x, lab):
+    return torch.stack([eng.rotate(x, ANGLES, mode='constant'), eng.rotate(lab, ANGLES, mode='nearest')]).cpu().numpy()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'r10_rotate.json'))
+    ap.add_argument('--host-reps', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=20)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'rotate_bench needs the GPU'
+    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    x4, lab, _ = synthetic_slices(S, R, R, seed=7, lesions=True)
+    x, lab = np.ascontiguousarray(x4[..., 0], np.float32), (np.asarray(lab) > 0).astype(np.float32)
+    res = {'workload': f'{S} slices of {R}x{R}, rotations {list(ROTATIONS)}: image (constant) + label map (nearest, fp32)', 'scipy': scipy.__version__,
+           'device': torch.cuda.get_device_name(0)}
+    res['host'] = stats(timed(lambda: host_rotate(x, lab), a.host_reps, 1))
+    res['device_with_upload'] = stats(timed(lambda: device_rotate(eng, x, lab), a.reps, 3))
+    xd, ld = torch.from_numpy(x).to(eng.device), torch.from_numpy(lab).to(eng.device)
+    res['device_resident'] = stats(timed(lambda: device_rotate(eng, xd, ld), a.reps, 3))
+    # agreement at the timed size (the GPU tests hold the bars; this is the record beside the timing)
+    got = device_rotate(eng, x, lab)
+    ks = range(0, S, 10)
+    res['agreement'] = {
+        'image_max_abs_err': float(max(np.abs(got[0][k, j] - scipy.ndimage.rotate(x[k].astype(np.float64), ang, reshape=False)).max()
+                                       for k in ks for j, ang in enumerate(ANGLES))),
+        'label_max_abs_err': float(max(np.abs(got[1][k, j] - scipy.ndimage.rotate(lab[k].astype(np.float64), ang, reshape=False, mode='nearest')).max()
+                                       for k in ks for j, ang in enumerate(ANGLES))),
+        'slices_checked': len(ks)}
+    res['speedup_with_upload'] = res['host']['median_ms'] / res['device_with_upload']['median_ms']
+    res['speedup_resident'] = res['host']['median_ms'] / res['device_resident']['median_ms']
+    # bytes one call must move at least: fp32 in, fp64 coefficients written by the column pass and read + rewritten by the row pass, read once
+    # by the gather (the 16 taps of a pixel overlap its neighbours'), 4-byte out per angle
+    pad = 12
+    res['bytes_model'] = {mode: S * R * R * 4 + 4 * S * (R + 2 * p) ** 2 * 8 + len(ANGLES) * S * R * R * 4 for mode, p in (('constant', 0), ('nearest', pad))}
+    eng.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

@@ -74,6 +74,16 @@ def zoom_output_hw(in_hw, factors):
     return tuple(int(round(i * z)) for i, z in zip(in_hw, f))
 
 
+def rotation_transform(angle, in_hw):
+    """(matrix [2,2], offset [2]) that scipy.ndimage.rotate(a, angle, reshape=False) hands to affine_transform for a [h,w] slice, formed with
+    scipy's own numpy expressions (cosdg / sindg, the M @ v product) so that the doubles are the same bit for bit."""
+    from scipy.special import cosdg, sindg
+    c, s = cosdg(angle), sindg(angle)
+    m = np.array([[c, s], [-s, c]])
+    in_center = (np.asarray(in_hw) - 1) / 2
+    return m, in_center - m @ in_center
+
+
 class _EvalOps(OrderStatOps):
     """Model-independent device ops of the evaluation path (erosion, 3-D median, residual maps, sort-based metrics, order statistics); shared
     by the AE-family Engine and the f-AnoGAN GanEngine.  Needs self.lib, self.device, self._dev, self._stream.
@@ -121,6 +131,50 @@ class _EvalOps(OrderStatOps):
         _lib.check(self.lib.uad_zoom_spline3(_ptr(s), n, h, w, H, W, boundary, _lib.ZOOM_I32 if integer else _lib.ZOOM_F32, _ptr(out), _ptr(ws),
                                              nbytes, self._stream()))
         return out
+
+    def affine(self, slices, matrices, offsets, out_hw=None, mode='constant', integer=False):
+        """scipy.ndimage.affine_transform(s, M, offset, output_shape=out_hw, order=3, mode=mode) of every slice of a [n,h,w] array / tensor
+        under each of K <= 16 transforms on the device (uad_affine_spline3; one spline prefilter serves all K) -> [n,K,H,W].  matrices [K,2,2]
+        (or one [2,2]), offsets [K,2] (or one [2]): output pixel (Y,X) reads input coordinate M @ (Y,X) + offset.  out_hw None = (h,w).
+        mode 'constant' (cval 0) | 'nearest'; integer as in zoom (int32, the spline rounded half away from zero)."""
+        if mode not in ('constant', 'nearest'):
+            raise ValueError(f"affine mode must be 'constant' or 'nearest', got {mode!r}")
+        s = slices if isinstance(slices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(slices, np.float32))
+        s = s.to(self.device, torch.float32).contiguous()
+        if s.dim() != 3:
+            raise ValueError(f'slices must be [n,h,w], got {tuple(s.shape)}')
+        m = np.asarray(matrices, np.float64)
+        o = np.asarray(offsets, np.float64)
+        if m.ndim == 2:
+            m, o = m[None], o[None]
+        if m.ndim != 3 or m.shape[1:] != (2, 2) or o.shape != (m.shape[0], 2):
+            raise ValueError(f'matrices must be [K,2,2] with offsets [K,2], got {m.shape} / {o.shape}')
+        K = m.shape[0]
+        if not 1 <= K <= _lib.AFFINE_MAX_K:
+            raise ValueError(f'1 .. {_lib.AFFINE_MAX_K} transforms a call, got {K}')
+        n, h, w = s.shape
+        H, W = (h, w) if out_hw is None else (int(v) for v in out_hw)
+        out = torch.empty((n, K, H, W), device=self.device, dtype=torch.int32 if integer else torch.float32)
+        xf = np.ascontiguousarray(np.concatenate([m.reshape(K, 4), o], axis=1))          # m00 m01 m10 m11 off0 off1
+        boundary = _lib.ZOOM_NEAREST if mode == 'nearest' else _lib.ZOOM_CONSTANT
+        if n == 0:
+            return out
+        nbytes = int(self.lib.uad_affine_spline3_workspace(n, h, w, boundary))
+        ws = torch.empty(max(nbytes // 8, 1), device=self.device, dtype=torch.float64)       # stream-ordered caching allocator: safe to drop after the launch
+        _lib.check(self.lib.uad_affine_spline3(_ptr(s), n, h, w, H, W, xf.ctypes.data_as(C.POINTER(C.c_double)), K, boundary,
+                                               _lib.ZOOM_I32 if integer else _lib.ZOOM_F32, _ptr(out), _ptr(ws), nbytes, self._stream()))
+        return out
+
+    def rotate(self, slices, angles, mode='constant', integer=False):
+        """scipy.ndimage.rotate(s, angle, reshape=False, order=3, mode=mode) of every slice of a [n,h,w] array / tensor for each of up to 16
+        angles [degrees] -> [n,K,h,w] (dataloaders/BRAINWEB.py:156-162: the `rotations` augmentation, 'nearest' for the label map).  Matrix and
+        offset are formed with scipy's own expressions, so the six doubles are scipy's bit for bit (90 and 180 degrees give exact 0 / +-1).
+        Angles that are multiples of 360 are not special-cased: the caller skips them."""
+        s = slices if isinstance(slices, torch.Tensor) else np.asarray(slices)
+        if s.ndim != 3:
+            raise ValueError(f'slices must be [n,h,w], got {tuple(s.shape)}')
+        ms, offs = zip(*(rotation_transform(a, s.shape[1:]) for a in np.atleast_1d(np.asarray(angles, np.float64)))) if np.size(angles) else ((), ())
+        return self.affine(s, np.array(ms).reshape(-1, 2, 2), np.array(offs).reshape(-1, 2), None, mode=mode, integer=integer)
 
     def mc_stats(self, recs, mask=None):
         """Monte-Carlo dropout statistics (utils/Evaluation.py:238-266): recs [K, ...] device / host array of K reconstructions, mask

@@ -180,7 +180,7 @@ def crop_center(img, cropx, cropy):
 
 def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0, slice_end=155, slice_resolution=None, skull_stripping=True,
                      view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None,
-                     device_stats=None):
+                     device_stats=None, device_rotate=None):
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
     map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
@@ -189,7 +189,12 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     device_stats (default: on when `engine` has the order-statistic ops, engine._EvalOps.select_quantiles): the masked volume is moved to
     slice-major order and uploaded ONCE as fp32, normalised there (_normalize_scaling_on), the empty-slice filter is one segmented select with
     one segment per slice, and the kept slices are padded and resampled from the device-resident volume -- no second upload of the image.
-    The label path is unchanged.  Same kept slices and the same bits as device_stats=False."""
+    The label path is unchanged.  Same kept slices and the same bits as device_stats=False.
+    device_rotate (default: on when `engine` has the `rotate` op, engine._EvalOps.rotate): the rotations run on the device -- the resampled
+    batch stays there after engine.zoom, one rotate call for the images ('constant') and one for the label maps ('nearest', fp32; they are not
+    thresholded again, as on the host) cover all non-zero angles, angle 0 passes through, center_crop is a slice of the result and both maps come
+    back in ONE download -- instead of two scipy.ndimage.rotate calls per slice and angle.  Same order (slice-major, angle-minor); values
+    within the fp32 rounding of the host loop's.  Without a non-zero angle, with engine=None or a stand-in without the op: the host loop."""
     from scipy.ndimage import rotate, zoom
     if denoise:
         raise NotImplementedError("nii.denoise() is SimpleITK's CurvatureFlow filter (MSLUB.py:257); it is not restated here")
@@ -206,6 +211,11 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
         device_stats = _has_order_stats(engine)
     elif device_stats and not _has_order_stats(engine):
         raise ValueError('device_stats needs an engine with the order-statistic ops (select_quantiles, clamp_scale)')
+    if device_rotate is None:
+        device_rotate = hasattr(engine, 'rotate')
+    elif device_rotate and not hasattr(engine, 'rotate'):
+        raise ValueError('device_rotate needs an engine with the rotate op')
+    device_rotate = bool(device_rotate) and any(a != 0 for a in rotations)
     vol_dev = keep_dev = None
     if device_stats:
         vol_dev = _normalize_scaling_on(engine, engine._dev(np.ascontiguousarray(np.moveaxis(vol, ax, 0), np.float32)), 0, 99.8)
@@ -250,10 +260,18 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     if engine is not None and slice_resolution is not None and len(sds):
         f = float(slice_resolution[0]) / float(sds[0].shape[0])
         hw = tuple(int(round(i * f)) for i in sds[0].shape)                 # scipy.ndimage.zoom's output shape
-        sds = list(engine.zoom(sds if device_stats else np.stack(sds), hw, mode='constant').cpu().numpy())
-        sss = list((engine.zoom(np.stack(sss), hw, mode='nearest').cpu().numpy().astype(np.float64) >= 0.9).astype(np.float64))
-    elif device_stats and len(sds):
+        sds = engine.zoom(sds if device_stats else np.stack(sds), hw, mode='constant')
+        sss = engine.zoom(np.stack(sss), hw, mode='nearest')
+        if device_rotate:
+            import torch
+            sss = (sss.to(torch.float64) >= 0.9).to(torch.float32)          # the host line below, on the resident batch
+        else:
+            sds = list(sds.cpu().numpy())
+            sss = list((sss.cpu().numpy().astype(np.float64) >= 0.9).astype(np.float64))
+    elif device_stats and len(sds) and not device_rotate:
         sds = list(sds.cpu().numpy())
+    if device_rotate and len(sds):
+        return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop)
     imgs, labs, kept = [], [], []
     for sd, ss, s in zip(sds, sss, kept_s):
         for angle in rotations:
@@ -264,6 +282,34 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     if not imgs:
         return np.zeros((0, 0, 0), np.float32), np.zeros((0, 0, 0), np.float32), []
     return np.stack(imgs), np.stack(labs), kept
+
+
+def _rotate_on(engine, images, labels, kept_s, rotations, center_crop):
+    """volume_to_slices' rotation step on the device: images / labels [k,H,W] (device tensors, or host arrays where no device step came before)
+    -> the (images, labels, kept) volume_to_slices returns.  engine.rotate takes up to 16 angles a call."""
+    import torch
+    angles = [a for a in rotations if a != 0]
+    out = []
+    for batch, mode in ((images, 'constant'), (labels, 'nearest')):
+        rot = torch.cat([engine.rotate(batch, angles[i:i + 16], mode=mode) for i in range(0, len(angles), 16)], dim=1)
+        plain = torch.as_tensor(np.stack(batch) if isinstance(batch, list) else batch, dtype=torch.float32, device=rot.device)
+        full = rot.new_empty((rot.shape[0], len(rotations)) + tuple(rot.shape[2:]))
+        k = 0
+        for j, a in enumerate(rotations):
+            if a == 0:
+                full[:, j] = plain
+            else:
+                full[:, j] = rot[:, k]
+                k += 1
+        out.append(full)
+    both = torch.stack(out)                                                 # [2, k, R, H, W]
+    if center_crop is not None:                                             # crop_center, as a slice of the batch
+        y, x = both.shape[-2:]
+        sx, sy = x // 2 - center_crop[0] // 2, y // 2 - center_crop[1] // 2
+        both = both[..., sy:sy + center_crop[1], sx:sx + center_crop[0]]
+    both = both.contiguous().cpu().numpy()                                            # the one download
+    both = both.reshape(2, -1, both.shape[-2], both.shape[-1])              # slice-major, angle-minor
+    return both[0], both[1], [s for s in kept_s for _ in rotations]
 
 
 def partition_patients(n_patients, partition=None, rng=None):
