@@ -24,6 +24,8 @@
  *   uad_erode_cross / uad_median3d / uad_scores_*
  *       <- utils/Evaluation.py:84-89 (scipy binary_erosion), :108-110 (scipy median_filter), trainers/Metrics.py:17-19,45-47,
  *          67-72,138-162 (sklearn AUPRC / AUROC, Dice threshold sweep)
+ *   uad_curvature_flow
+ *       <- utils/NII.py:85-87 (nii.denoise(): sitk.CurvatureFlow, called by dataloaders/MSLUB.py:242 and its siblings)
  *   uad_set_params / uad_get_params / uad_tensor_info
  *       <- tf.global_variables_initializer / tf.train.Saver variable access (trainers/DLMODEL.py:63-110)
  *   uad_op_*  — single-kernel entry points used by the parity tests (no reference counterpart).
@@ -359,6 +361,21 @@ enum { UAD_AFFINE_MAX_K = 16 };
 size_t uad_affine_spline3_workspace(int n, int h, int w, int boundary);
 int uad_affine_spline3(const float* in, int n, int h, int w, int H, int W, const double* xf, int K, int boundary, int out_kind, void* out,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- curvature-flow denoising of a volume (csrc/uad_flow.hip) <- utils/NII.py:85-87, nii.denoise() ------------------------------
+ * uad_curvature_flow: sitk.CurvatureFlow(image, timeStep = time_step, numberOfIterations = iterations) of one [nz,ny,nx] volume as
+ *   utils/curvature_flow.py states it from ITK's CurvatureFlowFunction::ComputeUpdate (that statement has not been compared with
+ *   SimpleITK's own output): per iteration one Jacobi sweep of a 19-point fp64 stencil, differences of dimension i scaled by
+ *   1 / spacing_xyz[i] (HOST array, x y z), neighbours clamped per axis, update 0 where the squared gradient is below 1e-9.  Every
+ *   operation is one IEEE fp64 add, multiply or divide in the host statement's order without fused multiply-adds: the result equals the
+ *   host statement's bit for bit.  in: DEVICE fp64, or fp32 (in_is_f32 != 0; widened exactly); out: DEVICE fp64, may not alias in.
+ *   iterations = 0 copies.  One launch per iteration; iterations >= 2 ping-pong between out and workspace: device memory of at least
+ *   uad_curvature_flow_workspace(nz, ny, nx) bytes (one fp64 volume), owned by the caller, free once the call's work on `stream` is
+ *   done; it may be NULL for iterations < 2.  UAD_ERR_INVALID: a non-positive dimension, a non-positive or non-finite spacing,
+ *   negative iterations, NULL or aliased pointers. */
+size_t uad_curvature_flow_workspace(int nz, int ny, int nx);
+int uad_curvature_flow(const void* in, int in_is_f32, int nz, int ny, int nx, const double spacing_xyz[3], double time_step, int iterations,
+                       double* out, void* workspace, void* stream);
 
 /* ---- order statistics without a sort (csrc/uad_select.hip) ----------------------------------------------------
  * uad_select_quantiles: segmented radix select over fp32 `in` [n_seg, n_per_seg] (device, contiguous).  For each segment: m = the number

@@ -1,0 +1,148 @@
+"""GPU: the device curvature-flow filter (uad_curvature_flow through engine._EvalOps.curvature_flow) and the ingestion on it
+(nifti.volume_to_slices(curvature_flow=...), nifti.build_cache).
+
+The reference is always the host statement utils/curvature_flow.py (pinned by tests/test_flow_host.py), never the code under test; volumes
+and references come from tests/flow_cases.py, computed once and shared.  The kernel performs the host statement's IEEE fp64 operations in
+the same order with contraction off and hipcc's correctly rounded division, so the bar of the op is BIT EQUALITY.  The ingestion after the
+filter is compared at the bars of tests/test_gpu_resample.py: the same kept slices, images within 1.2e-7 (the final fp32 rounding of the
+device resampler), label maps equal."""
+import numpy as np
+import pytest
+import scipy.ndimage
+import torch
+
+from tests import flow_cases as fc
+
+pytestmark = pytest.mark.gpu
+
+try:
+    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.utils import nifti
+    from unsupervised_anomaly_detection_brain_mri_amd.utils.curvature_flow import curvature_flow
+except Exception:
+    Engine = None
+
+F32_BAR = 1.2e-7            # tests/test_gpu_resample.py
+
+
+@pytest.fixture(scope='module')
+def eng():
+    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize('shape', fc.SHAPES, ids=lambda s: '%dx%dx%d' % s)
+def test_device_result_has_the_bits_of_the_host_statement(eng, shape):
+    for spacing in fc.SPACINGS:
+        for it in fc.ITERATIONS:
+            for f32 in (False, True):
+                src = fc.volume_f32(shape) if f32 else fc.volume(shape)
+                got = eng.curvature_flow(src.copy(), spacing, fc.TIME_STEP, it)
+                assert got.dtype == torch.float64 and tuple(got.shape) == shape and got.is_cuda
+                ref = fc.reference(shape, spacing, it, f32)
+                g = got.cpu().numpy()
+                print(f'flow {shape} spacing {spacing} it {it} f32 {f32}: {np.count_nonzero(g.view(np.uint64) != ref.view(np.uint64))} voxels differ, '
+                      f'max-abs {np.abs(g - ref).max():.3e}')
+                assert fc.same_bits(g, ref), (spacing, it, f32)
+
+
+def test_the_gate_taken_inside_a_wave(eng):
+    for spacing in fc.SPACINGS:
+        for it in fc.ITERATIONS:
+            assert fc.same_bits(eng.curvature_flow(fc.half_constant().copy(), spacing, fc.TIME_STEP, it).cpu().numpy(), fc.half_constant_reference(spacing, it))
+
+
+def test_a_smaller_volume_after_a_larger_one_and_a_repeat(eng):
+    big, small, sp = (33, 16, 64), (3, 7, 9), fc.SPACINGS[1]
+    a = eng.curvature_flow(fc.volume(big).copy(), sp, fc.TIME_STEP, 3)
+    b = eng.curvature_flow(fc.volume(small).copy(), sp, fc.TIME_STEP, 3)          # the allocator hands the larger call's blocks back
+    a2 = eng.curvature_flow(fc.volume(big).copy(), sp, fc.TIME_STEP, 3)
+    assert fc.same_bits(b.cpu().numpy(), fc.reference(small, sp, 3))
+    assert fc.same_bits(a.cpu().numpy(), fc.reference(big, sp, 3)) and torch.equal(a.view(torch.int64), a2.view(torch.int64))
+
+
+def test_device_input_stays_untouched_and_other_iteration_counts(eng):
+    shape, sp = (17, 17, 65), fc.SPACINGS[1]
+    src = torch.from_numpy(fc.volume(shape).copy()).to(eng.device)
+    keep = src.clone()
+    for it in (0, 2):
+        got = eng.curvature_flow(src, sp, fc.TIME_STEP, it)
+        assert got.data_ptr() != src.data_ptr() and fc.same_bits(got.cpu().numpy(), fc.reference(shape, sp, it))
+    assert torch.equal(src, keep)
+    assert fc.same_bits(eng.curvature_flow(fc.volume_f32(shape).copy(), sp, fc.TIME_STEP, 0).cpu().numpy(), fc.volume_f32(shape).astype(np.float64))
+    for bad in (dict(spacing=(1, 0, 1)), dict(spacing=(1, float('nan'), 1)), dict(spacing=(1, 1)), dict(iterations=-1)):
+        with pytest.raises(ValueError):
+            eng.curvature_flow(src, **bad)
+    with pytest.raises(ValueError):
+        eng.curvature_flow(src[0])
+
+
+def _phantom(seed, shape=(40, 40, 40)):
+    """tests/test_nifti.py's phantom, 40 voxels a side."""
+    rng = np.random.default_rng(seed)
+    z, y, x = np.meshgrid(*[np.linspace(-1, 1, s) for s in shape], indexing='ij')
+    brain = (x ** 2 + y ** 2 + (z * 0.8) ** 2) < 0.7
+    vol = (500 + 200 * x + 100 * rng.standard_normal(shape)) * brain + 30 * rng.random(shape)
+    seg = ((x - 0.2) ** 2 + (y + 0.1) ** 2 + z ** 2 < 0.03).astype(np.float32)
+    return vol, seg, brain.astype(np.float32)
+
+
+@pytest.mark.parametrize('device_stats', [True, False], ids=['device_stats', 'host_stats'])
+def test_volume_to_slices_with_the_filter_on_the_device_against_the_host_call(eng, device_stats):
+    vol, seg, brain = _phantom(1)
+    kw = dict(slice_start=4, slice_end=36, slice_resolution=(32, 32))
+    sp = (0.5, 0.5, 3.0)
+    im_h, lb_h, kept_h = nifti.volume_to_slices(vol, seg, brain, curvature_flow=True, spacing=sp, **kw)
+    # the condition on the label input, on scipy alone (tests/test_gpu_resample.py): the device label map is fp32 before the 0.9 cut
+    un = np.stack([scipy.ndimage.zoom((seg[s] >= 0.9).astype(np.float64), 32 / 40.0, mode='nearest') for s in kept_h])
+    assert np.count_nonzero(np.abs(un - 0.9) < F32_BAR) == 0
+    im_d, lb_d, kept_d = nifti.volume_to_slices(vol, seg, brain, curvature_flow=True, spacing=sp, engine=eng, device_stats=device_stats, **kw)
+    assert kept_d == kept_h and len(kept_h) > 8 and im_d.shape == im_h.shape and im_d.dtype == im_h.dtype and lb_d.dtype == lb_h.dtype
+    err = float(np.abs(im_d.astype(np.float64) - im_h.astype(np.float64)).max())
+    print(f'volume_to_slices(curvature_flow=True, device_stats={device_stats}) images: max-abs err {err:.3e}')
+    assert err <= F32_BAR
+    assert np.array_equal(lb_d, lb_h)
+    # the filter changed the pixels, and switching it off gives the path of before, bit for bit
+    off_h = nifti.volume_to_slices(vol, seg, brain, engine=eng, device_stats=device_stats, **kw)
+    off_n = nifti.volume_to_slices(vol, seg, brain, curvature_flow=None, spacing=sp, engine=eng, device_stats=device_stats, **kw)
+    assert off_n[2] == off_h[2] and np.array_equal(off_n[0].view(np.uint32), off_h[0].view(np.uint32)) and np.array_equal(off_n[1], off_h[1])
+    assert off_h[2] != kept_d or np.abs(off_h[0] - im_d).max() > 1e-3
+    # without resampling nothing but the filter, the skull map and the scaling is left: the device path returns the host's values
+    raw = dict(slice_start=4, slice_end=36, slice_resolution=None)
+    r_h = nifti.volume_to_slices(vol, seg, brain, curvature_flow=(2, 0.125), spacing=sp, **raw)
+    r_d = nifti.volume_to_slices(vol, seg, brain, curvature_flow=(2, 0.125), spacing=sp, engine=eng, device_stats=device_stats, **raw)
+    assert r_d[2] == r_h[2] and np.array_equal(r_d[0], r_h[0])
+
+
+def test_build_cache_with_the_filter_and_the_header_spacing(eng, tmp_path):
+    from unsupervised_anomaly_detection_brain_mri_amd.utils.slice_cache import read_cache
+    patients, sp = [], (0.5, 0.5, 3.0)
+    for i in range(2):
+        vol, seg, brain = _phantom(30 + i, (12, 40, 40))
+        d = tmp_path / f'p{i}'
+        d.mkdir()
+        nifti.write_nifti(str(d / 'flair.nii.gz'), vol, pixdim=sp)
+        nifti.write_nifti(str(d / 'gt.nii.gz'), seg, dtype='u1', pixdim=sp)
+        nifti.write_nifti(str(d / 'mask.nii.gz'), brain, dtype='u1', pixdim=sp)
+        patients.append({'name': f'p{i}', 'volume': str(d / 'flair.nii.gz'), 'groundtruth': str(d / 'gt.nii.gz'), 'skullmap': str(d / 'mask.nii.gz')})
+    kw = dict(partition={'TRAIN': 0.5, 'VAL': 0.5}, seed=0, engine=eng, slice_start=1, slice_end=11, slice_resolution=(32, 32))
+    nifti.build_cache(str(tmp_path / 'flow'), patients, curvature_flow=True, **kw)
+    nifti.build_cache(str(tmp_path / 'plain'), patients, **kw)
+    a, _, ia = read_cache(str(tmp_path / 'flow'))
+    b, _, _ = read_cache(str(tmp_path / 'plain'))
+    assert a.shape != b.shape or np.abs(a - b).max() > 1e-3
+    # the host pipeline by hand with the header's spacing (unit spacing would give other pixels)
+    want, unit = [], []
+    for p in patients:
+        vol, seg, brain = (nifti.read_nifti(p[k])[0] for k in ('volume', 'groundtruth', 'skullmap'))
+        want.append(nifti.volume_to_slices(curvature_flow(vol, sp), seg, brain, slice_start=1, slice_end=11, slice_resolution=(32, 32)))
+        unit.append(nifti.volume_to_slices(curvature_flow(vol), seg, brain, slice_start=1, slice_end=11, slice_resolution=(32, 32)))
+    order = [int(n[1:]) for n in dict.fromkeys(ia['patients'])]
+    w = np.concatenate([want[i][0] for i in order])
+    assert a.shape[:3] == w.shape
+    err = float(np.abs(a[..., 0].astype(np.float64) - w).max())
+    print(f'build_cache(curvature_flow=True) against the host pipeline by hand: max-abs err {err:.3e}')
+    assert err <= F32_BAR
+    u = np.concatenate([unit[i][0] for i in order])
+    assert u.shape != w.shape or np.abs(u - w).max() > 1e-3

@@ -3,8 +3,11 @@
 
     python tools/build_cache.py <root> <cache_dir> --protocol FLAIR --res 128 --start 15 --end 125
 
-The volume -> slice steps are those of utils/nifti.py (skull stripping, percentile scaling, empty-slice filter, pad / zoom); the ITK
-CurvatureFlow denoising of the reference loaders is not applied.  --device-resample runs the pad / zoom step's cubic spline on the GPU;
+The volume -> slice steps are those of utils/nifti.py (skull stripping, percentile scaling, empty-slice filter, pad / zoom).
+--curvature-flow [ITER STEP] applies the curvature-flow denoising of the reference loaders (nii.denoise(), utils/NII.py:85-87; without
+values: 3 iterations of time step 0.125) to every volume before skull stripping, with the voxel spacing of its header; on the device
+(uad_curvature_flow) when an engine is used, else utils/curvature_flow.py on the host -- the same bits.  That arithmetic is ITK's update
+written down from its source and has not been compared with SimpleITK's own output.  --device-resample runs the pad / zoom step's cubic spline on the GPU;
 --device-stats also runs the percentile scaling and the empty-slice filter there (one upload per volume, resampled slices come back).
 --rotations A [A ...]: the rotation augmentation of the reference's dataset classes (dataloaders/BRAINWEB.py:156-162), one cached slice per
 angle; with a device engine the rotations run there too (uad_affine_spline3).  The default, 0, caches the unrotated slices only.
@@ -33,7 +36,12 @@ def main():
                     help='percentile scaling and empty-slice filter on the device select op (uad_select_quantiles); implies --device-resample')
     ap.add_argument('--rotations', type=float, nargs='+', default=[0], metavar='A',
                     help='angles in degrees, one cached slice per angle and kept slice (0 = unrotated; on the device when an engine is used)')
+    ap.add_argument('--curvature-flow', nargs='*', default=None, metavar=('ITER', 'STEP'),
+                    help='curvature-flow denoising before skull stripping; no values = 3 iterations of time step 0.125 (nii.denoise())')
     a = ap.parse_args()
+    if a.curvature_flow is not None and len(a.curvature_flow) not in (0, 2):
+        ap.error('--curvature-flow takes no values or ITER STEP')
+    flow = None if a.curvature_flow is None else (True if not a.curvature_flow else (int(a.curvature_flow[0]), float(a.curvature_flow[1])))
     patients = []
     for name in sorted(os.listdir(a.root)):
         d = os.path.join(a.root, name)
@@ -50,7 +58,7 @@ def main():
         engine = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)       # any handle carries the model-independent device ops
     info = nifti.build_cache(a.cache, patients, partition={'TRAIN': a.train, 'VAL': a.val, 'TEST': a.test}, seed=a.seed, engine=engine, axis=a.axis,
                              slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'rotations': tuple(a.rotations)} if list(a.rotations) != [0] else {}),
-                             **({'device_stats': a.device_stats} if engine is not None else {}))
+                             **({'device_stats': a.device_stats} if engine is not None else {}), **({'curvature_flow': flow} if flow is not None else {}))
     print(json.dumps(info))
 
 

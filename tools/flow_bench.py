@@ -1,0 +1,99 @@
+"""Host numpy against the device curvature-flow filter (uad_curvature_flow) on the denoising step of the slice ingestion.
+
+    python tools/flow_bench.py [--out profiles/r11_flow.json] [--host-reps 3] [--reps 20]
+
+Workload: nii.denoise() (utils/NII.py:85-87: three iterations, time step 0.125) of one 110 x 217 x 181 volume and one 192 x 512 x 512
+volume of fp64 voxels, spacing (1, 1, 1).
+  host             utils/curvature_flow.py (vectorised numpy); host clock.
+  device           engine.curvature_flow on a host array: H2D of the fp64 volume + three launches, then a synchronise (the result stays on the
+                   device, as in nifti.volume_to_slices with device_stats on); host clock.
+  device_resident  the same call on a device-resident volume; host clock around the call and a synchronise.
+Every timed shape is warmed up first; median / min / max over the repetitions are reported (the host path: no warm-up, 3 repetitions).
+Beside the times: the bytes per second the resident path achieves against the 16 B per voxel and iteration the stencil must move (one fp64
+read, one fp64 write), and whether the device result has the host statement's bits.  No threshold is set here.  Needs the GPU: there is
+no fallback."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.utils.curvature_flow import curvature_flow  # noqa: E402
+
+SHAPES = ((110, 217, 181), (192, 512, 512))
+ITERATIONS, TIME_STEP, SPACING = 3, 0.125, (1.0, 1.0, 1.0)
+
+
+def stats(ms):
+    return {'median_ms': statistics.median(ms), 'min_ms': min(ms), 'max_ms': max(ms), 'reps': len(ms)}
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'r11_flow.json'))
+    ap.add_argument('--host-reps', type=int, default=3)
+    ap.add_argument('--reps', type=int, default=20)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'flow_bench needs the GPU'
+    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    res = {'workload': f'curvature flow, {ITERATIONS} iterations, time step {TIME_STEP}, spacing {list(SPACING)}, fp64 volumes', 'numpy': np.__version__,
+           'device': torch.cuda.get_device_name(0), 'cases': {}}
+
+    def on_device(v):
+        out = eng.curvature_flow(v, SPACING, TIME_STEP, ITERATIONS)
+        torch.cuda.synchronize()
+        return out
+
+    for shape in SHAPES:
+        name = 'x'.join(map(str, shape))
+        vol = np.random.default_rng(11).random(shape) * 1000.0
+        case = {'voxels': int(vol.size)}
+        host = {}
+
+        def on_host():
+            host['out'] = curvature_flow(vol, SPACING, TIME_STEP, ITERATIONS)
+        case['host'] = stats(timed(on_host, a.host_reps, 0))
+        print(f'{name}: host {case["host"]["median_ms"]:.1f} ms', flush=True)
+        case['device_with_upload'] = stats(timed(lambda: on_device(vol), a.reps, 3))
+        vd = torch.from_numpy(vol).to(eng.device)
+        case['device_resident'] = stats(timed(lambda: on_device(vd), a.reps, 3))
+        got = on_device(vd).cpu().numpy()
+        case['bit_equal_to_host'] = bool(np.array_equal(got.view(np.uint64), host['out'].view(np.uint64)))
+        case['max_abs_diff'] = float(np.abs(got - host['out']).max())
+        must = 16 * vol.size * ITERATIONS                      # one fp64 read + one fp64 write per voxel and iteration
+        case['bytes_must_move'] = must
+        case['achieved_GBps_resident'] = must / (case['device_resident']['median_ms'] * 1e-3) / 1e9
+        case['speedup_with_upload'] = case['host']['median_ms'] / case['device_with_upload']['median_ms']
+        case['speedup_resident'] = case['host']['median_ms'] / case['device_resident']['median_ms']
+        res['cases'][name] = case
+        print(f'{name}: device with upload {case["device_with_upload"]["median_ms"]:.3f} ms, resident {case["device_resident"]["median_ms"]:.3f} ms, '
+              f'{case["achieved_GBps_resident"]:.0f} GB/s of the 16 B model, bit-equal {case["bit_equal_to_host"]}', flush=True)
+        del vd, got, host
+    eng.close()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

@@ -134,6 +134,9 @@ SYMBOLS = {
     'uad_affine_spline3_workspace': (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'uad_affine_spline3': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'uad_curvature_flow_workspace': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'uad_curvature_flow': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     'uad_select_workspace': (C.c_size_t, [C.c_int]),
     'uad_select_quantiles': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.c_int, C.c_uint, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),

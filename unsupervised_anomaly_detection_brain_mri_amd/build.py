@@ -12,8 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, 'libuad_hip.so')
-SOURCES = ['uad_gemm.hip', 'uad_gemm_d16s.hip', 'uad_gemm_d16s3.hip', 'uad_misc.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_cc.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_allreduce.hip']
+SOURCES = ['uad_gemm.hip', 'uad_gemm_d16s.hip', 'uad_gemm_d16s3.hip', 'uad_misc.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_flow.hip', 'uad_cc.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_allreduce.hip']
 ARCH = 'gfx950'
+# per-file flags.  uad_flow.hip must return the bits of utils/curvature_flow.py: no multiply-add may be fused, in host or device code
+EXTRA_FLAGS = {'uad_flow.hip': ['-ffp-contract=off']}
 
 
 def _hipcc():
@@ -45,7 +47,7 @@ def build(force=False, verbose=False):
         src = os.path.join(CSRC, s)
         obj = os.path.join(objdir, s.replace('.hip', '.o'))
         if force or _newer([src] + headers, obj):
-            cmd = [hipcc] + flags + ['-c', src, '-o', obj]
+            cmd = [hipcc] + flags + EXTRA_FLAGS.get(s, []) + ['-c', src, '-o', obj]
             if verbose:
                 print(' '.join(cmd), file=sys.stderr)
             jobs.append(cmd)

@@ -176,6 +176,32 @@ class _EvalOps(OrderStatOps):
         ms, offs = zip(*(rotation_transform(a, s.shape[1:]) for a in np.atleast_1d(np.asarray(angles, np.float64)))) if np.size(angles) else ((), ())
         return self.affine(s, np.array(ms).reshape(-1, 2, 2), np.array(offs).reshape(-1, 2), None, mode=mode, integer=integer)
 
+    def curvature_flow(self, vol, spacing=(1, 1, 1), time_step=0.125, iterations=3):
+        """nii.denoise() (utils/NII.py:85-87: sitk.CurvatureFlow(timeStep=0.125, numberOfIterations=3)) of one [z,y,x] volume on the device
+        (uad_curvature_flow): the arithmetic of utils/curvature_flow.py -- ITK's update written down from its source, not yet compared with
+        SimpleITK's own output -- and its bits.  vol: host array or device tensor; float32 is uploaded as it is and widened exactly on the
+        device, everything else goes through float64.  spacing = (sx, sy, sz).  -> float64 device tensor [z,y,x]; the input is not modified."""
+        v = vol
+        if not isinstance(v, torch.Tensor):
+            a = np.asarray(v)
+            v = torch.from_numpy(np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64))
+        v = v.to(self.device, torch.float32 if v.dtype == torch.float32 else torch.float64).contiguous()
+        if v.dim() != 3 or v.numel() == 0:
+            raise ValueError(f'vol must be a non-empty [z,y,x] volume, got {tuple(v.shape)}')
+        if int(iterations) != iterations:
+            raise ValueError(f'iterations must be an integer, got {iterations!r}')
+        if len(spacing) != 3:
+            raise ValueError(f'spacing must be (sx, sy, sz), got {spacing!r}')
+        sp = (C.c_double * 3)(*(float(s) for s in spacing))
+        nz, ny, nx = v.shape
+        out = torch.empty((nz, ny, nx), device=self.device, dtype=torch.float64)
+        ws = None
+        if iterations >= 2:                                      # stream-ordered caching allocator: safe to drop after the launches
+            ws = torch.empty(int(self.lib.uad_curvature_flow_workspace(nz, ny, nx)) // 8, device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.uad_curvature_flow(_ptr(v), int(v.dtype == torch.float32), nz, ny, nx, sp, float(time_step), int(iterations), _ptr(out), _ptr(ws),
+                                               self._stream()))
+        return out
+
     def mc_stats(self, recs, mask=None):
         """Monte-Carlo dropout statistics (utils/Evaluation.py:238-266): recs [K, ...] device / host array of K reconstructions, mask
         broadcastable to one sample.  Returns (mean, epistemic variance) of the masked reconstructions as device tensors."""

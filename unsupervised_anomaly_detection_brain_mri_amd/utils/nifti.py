@@ -8,7 +8,10 @@ fastest), with `scl_slope * v + scl_inter` applied when the header asks for it a
 binarise the brain mask at 0.1 and multiply (skull stripping, NII.py:75-81), clamp to the [0, 99.8] percentiles and scale by the maximum
 (`normalize('scaling', 0, 99.8)`, NII.py:50-70), walk the slices `sliceStart .. sliceEnd` of the chosen view, drop the "empty" ones
 (90th percentile < 0.2, MSLUB.py:161), zero-pad to and `scipy.ndimage.zoom` onto `sliceResolution`, binarise the label slice at 0.9.
-NOT restated: `nii.denoise()` (SimpleITK's CurvatureFlow, three iterations) -- an ITK filter with no counterpart here; `denoise=True` raises.
+`nii.denoise()` (SimpleITK's CurvatureFlow, three iterations of time step 0.125; NII.py:85-87, called before skull stripping by MSLUB.py:242,
+MSISBI2015.py:231, MSSEG2008.py:241,246) is the keyword `curvature_flow` of `volume_to_slices`: utils/curvature_flow.py states ITK's update
+from its source, and csrc/uad_flow.hip runs the same arithmetic on the device with the same bits.  That statement has not been compared with
+SimpleITK's own output yet, which is why `denoise=True` still raises and the filter has a keyword of its own.
 
 `build_cache` turns a list of patients into the slice cache of utils/slice_cache.py with the reference's patient-level TRAIN / VAL / TEST
 partition (a permutation of the patients cut at floor(fraction * n), MSLUB.py:71-90)."""
@@ -180,7 +183,7 @@ def crop_center(img, cropx, cropy):
 
 def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0, slice_end=155, slice_resolution=None, skull_stripping=True,
                      view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None,
-                     device_stats=None, device_rotate=None):
+                     device_stats=None, device_rotate=None, curvature_flow=None, spacing=(1, 1, 1)):
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
     map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
@@ -194,23 +197,43 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     batch stays there after engine.zoom, one rotate call for the images ('constant') and one for the label maps ('nearest', fp32; they are not
     thresholded again, as on the host) cover all non-zero angles, angle 0 passes through, center_crop is a slice of the result and both maps come
     back in ONE download -- instead of two scipy.ndimage.rotate calls per slice and angle.  Same order (slice-major, angle-minor); values
-    within the fp32 rounding of the host loop's.  Without a non-zero angle, with engine=None or a stand-in without the op: the host loop."""
+    within the fp32 rounding of the host loop's.  Without a non-zero angle, with engine=None or a stand-in without the op: the host loop.
+    curvature_flow: None (off) | True = (3, 0.125) | (iterations, time_step): the reference's nii.denoise() (NII.py:85-87), applied to the
+    NaN-zeroed fp64 volume BEFORE skull stripping, which is where MSLUB.py:242 calls it; spacing = (sx, sy, sz), the voxel size the filter
+    scales its differences by (build_cache takes it from the NIfTI header).  The arithmetic is utils/curvature_flow.py's -- ITK's update written
+    down from its source, not yet compared with SimpleITK's own output.  With an engine that has the `curvature_flow` op
+    (engine._EvalOps.curvature_flow) it runs there, same bits; with device_stats on, the skull-strip multiply and the move to slice-major order
+    happen on the device too, so the volume is uploaded once and not downloaded in between.  Without such an engine: the host statement."""
     from scipy.ndimage import rotate, zoom
     if denoise:
         raise NotImplementedError("nii.denoise() is SimpleITK's CurvatureFlow filter (MSLUB.py:257); it is not restated here")
     vm = view_mapping or VIEW_MAPPING
     ax = vm[axis]
+    flow = _flow_setting(curvature_flow)
     vol = np.array(vol, np.float64)
     vol[np.isnan(vol)] = 0.0
     if seg is None:
         seg = np.zeros_like(vol)
     seg = (np.asarray(seg) >= 0.9).astype(np.float64)                       # MSLUB.py:264-265
-    if skull_stripping and brainmask is not None:
-        vol = vol * (np.asarray(brainmask) >= 0.1)                          # NII.apply_skullmap
     if device_stats is None:
         device_stats = _has_order_stats(engine)
     elif device_stats and not _has_order_stats(engine):
         raise ValueError('device_stats needs an engine with the order-statistic ops (select_quantiles, clamp_scale)')
+    flow_dev = None
+    if flow is not None:                                                    # nii.denoise(), before the skull map (MSLUB.py:242,257)
+        if hasattr(engine, 'curvature_flow'):
+            flow_dev = engine.curvature_flow(vol, spacing, time_step=flow[1], iterations=flow[0])
+            if not device_stats:
+                vol, flow_dev = flow_dev.cpu().numpy(), None
+        else:
+            from .curvature_flow import curvature_flow as flow_host
+            vol = flow_host(vol, spacing, time_step=flow[1], iterations=flow[0])
+    if skull_stripping and brainmask is not None:
+        if flow_dev is not None:                                            # (the host `vol` only lends its shape from here on)
+            import torch
+            flow_dev = flow_dev * torch.from_numpy(np.asarray(brainmask) >= 0.1).to(flow_dev.device, flow_dev.dtype)
+        else:
+            vol = vol * (np.asarray(brainmask) >= 0.1)                      # NII.apply_skullmap
     if device_rotate is None:
         device_rotate = hasattr(engine, 'rotate')
     elif device_rotate and not hasattr(engine, 'rotate'):
@@ -218,7 +241,12 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     device_rotate = bool(device_rotate) and any(a != 0 for a in rotations)
     vol_dev = keep_dev = None
     if device_stats:
-        vol_dev = _normalize_scaling_on(engine, engine._dev(np.ascontiguousarray(np.moveaxis(vol, ax, 0), np.float32)), 0, 99.8)
+        if flow_dev is not None:                                            # the host lines below, on the resident filtered volume
+            import torch
+            moved = flow_dev.movedim(ax, 0).to(torch.float32).contiguous()
+        else:
+            moved = engine._dev(np.ascontiguousarray(np.moveaxis(vol, ax, 0), np.float32))
+        vol_dev = _normalize_scaling_on(engine, moved, 0, 99.8)
         s_end = min(slice_end, vol.shape[ax])
         if s_end > slice_start:
             stat = engine.percentile(vol_dev[slice_start:s_end], empty_percentile, segments=s_end - slice_start)
@@ -284,6 +312,21 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     return np.stack(imgs), np.stack(labs), kept
 
 
+def _flow_setting(curvature_flow):
+    """volume_to_slices' `curvature_flow` keyword -> None | (iterations, time_step)."""
+    if curvature_flow is None or curvature_flow is False:
+        return None
+    if curvature_flow is True:
+        return 3, 0.125                                                     # NII.py:86
+    try:
+        iterations, time_step = curvature_flow
+    except (TypeError, ValueError):
+        raise ValueError(f'curvature_flow must be None, True or (iterations, time_step), got {curvature_flow!r}') from None
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError(f'curvature_flow: iterations must be a non-negative integer, got {iterations!r}')
+    return int(iterations), float(time_step)
+
+
 def _rotate_on(engine, images, labels, kept_s, rotations, center_crop):
     """volume_to_slices' rotation step on the device: images / labels [k,H,W] (device tensors, or host arrays where no device step came before)
     -> the (images, labels, kept) volume_to_slices returns.  engine.rotate takes up to 16 angles a call."""
@@ -328,7 +371,9 @@ def partition_patients(n_patients, partition=None, rng=None):
 
 def build_cache(directory, patients, partition=None, seed=0, engine=None, **slice_options):
     """patients: [{'name', 'volume': path, 'groundtruth': path or None, 'skullmap': path or None}] -> slice cache in `directory`.
-    slice_options: volume_to_slices keywords (device_stats among them); engine: volume_to_slices' device resampler / order statistics.
+    slice_options: volume_to_slices keywords (device_stats, curvature_flow among them); engine: volume_to_slices' device resampler / order
+    statistics / curvature flow.  Unless slice_options names a `spacing`, each volume gets its own from its header: abs(pixdim[1:4]), a zero
+    replaced by 1.0.
     Returns the index dict that was written."""
     from .slice_cache import SET_TYPES, write_cache
     split = partition_patients(len(patients), partition, np.random.default_rng(seed))
@@ -340,10 +385,11 @@ def build_cache(directory, patients, partition=None, seed=0, engine=None, **slic
     for i, p in enumerate(patients):
         if i not in set_of:
             continue
-        vol, _ = read_nifti(p['volume'])
+        vol, hdr = read_nifti(p['volume'])
         seg = read_nifti(p['groundtruth'])[0] if p.get('groundtruth') else None
         msk = read_nifti(p['skullmap'])[0] if p.get('skullmap') else None
-        im, lb, kept = volume_to_slices(vol, seg, msk, engine=engine, **slice_options)
+        spacing = tuple(abs(float(d)) or 1.0 for d in hdr['pixdim'][1:4])
+        im, lb, kept = volume_to_slices(vol, seg, msk, engine=engine, **{'spacing': spacing, **slice_options})
         if len(kept):
             images.append(im); labels.append(lb); sets += [set_of[i]] * len(kept); owner += [p.get('name', str(i))] * len(kept)
     if not images:
