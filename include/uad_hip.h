@@ -26,6 +26,8 @@
  *          67-72,138-162 (sklearn AUPRC / AUROC, Dice threshold sweep)
  *   uad_curvature_flow
  *       <- utils/NII.py:85-87 (nii.denoise(): sitk.CurvatureFlow, called by dataloaders/MSLUB.py:242 and its siblings)
+ *   uad_resize2d / uad_mask_by_label
+ *       <- dataloaders/BRAINWEB.py:140-142 (cv2.resize of slices larger than sliceResolution), :266-289 (skull map from the tissue classes)
  *   uad_set_params / uad_get_params / uad_tensor_info
  *       <- tf.global_variables_initializer / tf.train.Saver variable access (trainers/DLMODEL.py:63-110)
  *   uad_op_*  — single-kernel entry points used by the parity tests (no reference counterpart).
@@ -376,6 +378,29 @@ int uad_affine_spline3(const float* in, int n, int h, int w, int H, int W, const
 size_t uad_curvature_flow_workspace(int nz, int ny, int nx);
 int uad_curvature_flow(const void* in, int in_is_f32, int nz, int ny, int nx, const double spacing_xyz[3], double time_step, int iterations,
                        double* out, void* workspace, void* stream);
+
+/* ---- bilinear / nearest resize of slices and tissue-class masking (csrc/uad_resize.hip) <- dataloaders/BRAINWEB.py:140-142, 266-289 ----
+ * uad_resize2d: cv2.resize(a, (W, H)) with INTER_LINEAR (UAD_RESIZE_LINEAR) or INTER_NEAREST (UAD_RESIZE_NEAREST) of [h,w] fp32 slices as
+ *   utils/resize.py states it from OpenCV 4.2's resize.cpp (that statement has not been compared with OpenCV's own output).  Per axis
+ *   scale = 1.0 / ((double)dst / (double)src).  Linear: f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= (float)s in fp32, s < 0 ->
+ *   (0, 0), s >= src - 1 -> (src - 1, 0), taps s and min(s + 1, src - 1) weighted (1.0f - f, f); the horizontal pass first, then the vertical
+ *   one, every multiply and add one fp32 operation without fused multiply-adds.  Nearest: min(floor(d * scale), src - 1) in fp64 -- not
+ *   d * src / dst (22 -> 18: output 9 reads input 10) -- and the value's bits are copied.  The result equals the host statement's bit for bit.
+ *   in: DEVICE fp32 [n_in,h,w]; out: DEVICE fp32 [n,H,W], may not alias in.  Output slice j is the resize of input slice slice_idx[j]
+ *   (DEVICE int32 [n], any order, repeats allowed: the kept slices of a resident slice-major volume are resized where they lie); NULL =
+ *   identity, which needs n == n_in.  Entries outside [0, n_in) are the caller's error (engine.resize validates them on the host).
+ *   One launch, no workspace, no atomics, no host synchronisation: the per-axis tables are formed in the kernel, once per workgroup in LDS;
+ *   a slice's bits depend on neither n nor its position in the batch.  h, w, H, W, n, n_in >= 1.  UAD_ERR_INVALID: a non-positive size, an
+ *   unknown mode, NULL in / out, out aliasing in, NULL slice_idx with n != n_in.
+ *   UAD_ERR_UNSUPPORTED: more than one grid holds -- n > 65535 output slices or H > 524280 output rows (65535 row tiles of 8); split the call.
+ * uad_mask_by_label: out[i] = lut256[labels[i]] ? vol[i] : 0 (out may alias vol) and, unless lesion_out is NULL, lesion_out[i] =
+ *   labels[i] == lesion_label ? 1 : 0 -- load_volume_and_groundtruth's skull-map multiply and lesion binarisation (BRAINWEB.py:266-289) in
+ *   one pass over a tissue-class volume; the LUT idea of uad_gather_mask.  vol / out / lesion_out: DEVICE fp32 [n]; labels: DEVICE u8 [n];
+ *   lut256: DEVICE u8 [256].  A masked element is +0 whatever its sign was. */
+enum { UAD_RESIZE_LINEAR = 0, UAD_RESIZE_NEAREST = 1 };
+int uad_resize2d(const float* in, int n_in, int h, int w, const int* slice_idx, int n, int H, int W, int mode, float* out, void* stream);
+int uad_mask_by_label(const float* vol, const unsigned char* labels, long long n, const unsigned char* lut256, float* out, float* lesion_out,
+                      int lesion_label, void* stream);
 
 /* ---- order statistics without a sort (csrc/uad_select.hip) ----------------------------------------------------
  * uad_select_quantiles: segmented radix select over fp32 `in` [n_seg, n_per_seg] (device, contiguous).  For each segment: m = the number

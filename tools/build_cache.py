@@ -11,6 +11,13 @@ written down from its source and has not been compared with SimpleITK's own outp
 --device-stats also runs the percentile scaling and the empty-slice filter there (one upload per volume, resampled slices come back).
 --rotations A [A ...]: the rotation augmentation of the reference's dataset classes (dataloaders/BRAINWEB.py:156-162), one cached slice per
 angle; with a device engine the rotations run there too (uad_affine_spline3).  The default, 0, caches the unrotated slices only.
+--loader brainweb prepares the volumes the way the reference prepares its BrainWeb training set (dataloaders/BRAINWEB.py:125-185, 266-292;
+nifti.volume_to_slices(loader='brainweb')) instead of the MS datasets' way: --gt then names the TISSUE-CLASS file (values 0 .. 10), which
+supplies the skull map and the lesion map (== 10), and --mask is ignored; constant slices are dropped; a slice larger than --res is resized
+as cv2.resize does (bilinear image, nearest label; utils/resize.py, not compared with OpenCV itself, which is not a dependency), a smaller
+one zero-padded.  --no-skull-removal keeps FAT / MUSCLE / SKIN / SKULL / CONNECTIVE, --no-background-removal keeps BACKGROUND.  With a device
+engine (--device-resample or --device-stats) the whole path runs on the GPU (uad_mask_by_label, uad_select_quantiles, uad_resize2d).
+--curvature-flow is refused for this loader: the reference does not denoise BrainWeb.
 """
 import argparse
 import json
@@ -38,6 +45,10 @@ def main():
                     help='angles in degrees, one cached slice per angle and kept slice (0 = unrotated; on the device when an engine is used)')
     ap.add_argument('--curvature-flow', nargs='*', default=None, metavar=('ITER', 'STEP'),
                     help='curvature-flow denoising before skull stripping; no values = 3 iterations of time step 0.125 (nii.denoise())')
+    ap.add_argument('--loader', choices=('mslub', 'brainweb'), default='mslub',
+                    help="'brainweb': the training set's preparation; --gt names the tissue-class file, --mask is ignored")
+    ap.add_argument('--no-skull-removal', action='store_true', help='--loader brainweb: keep the skull tissue classes (4, 5, 6, 7, 9)')
+    ap.add_argument('--no-background-removal', action='store_true', help='--loader brainweb: keep the background class (0)')
     a = ap.parse_args()
     if a.curvature_flow is not None and len(a.curvature_flow) not in (0, 2):
         ap.error('--curvature-flow takes no values or ITER STEP')
@@ -49,16 +60,24 @@ def main():
         if not os.path.isfile(vol):
             continue
         gt, mk = os.path.join(d, f'{name}_{a.gt}.nii.gz'), os.path.join(d, f'{name}_{a.mask}.nii.gz')
+        if a.loader == 'brainweb':
+            mk = ''                                                    # the tissue classes are the skull map
         patients.append({'name': name, 'volume': vol, 'groundtruth': gt if os.path.isfile(gt) else None, 'skullmap': mk if os.path.isfile(mk) else None})
     if not patients:
         raise SystemExit(f'no <patient>/<patient>_{a.protocol}.nii.gz under {a.root}')
+    loader = {}
+    if a.loader == 'brainweb':
+        if flow is not None:
+            ap.error('--curvature-flow does not go with --loader brainweb')
+        loader = {'loader': 'brainweb', 'skull_removal': not a.no_skull_removal, 'background_removal': not a.no_background_removal}
     engine = None
     if a.device_resample or a.device_stats:
         from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
         engine = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)       # any handle carries the model-independent device ops
     info = nifti.build_cache(a.cache, patients, partition={'TRAIN': a.train, 'VAL': a.val, 'TEST': a.test}, seed=a.seed, engine=engine, axis=a.axis,
                              slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'rotations': tuple(a.rotations)} if list(a.rotations) != [0] else {}),
-                             **({'device_stats': a.device_stats} if engine is not None else {}), **({'curvature_flow': flow} if flow is not None else {}))
+                             **({'device_stats': a.device_stats} if engine is not None and not loader else {}), **({'curvature_flow': flow} if flow is not None else {}),
+                             **loader)
     print(json.dumps(info))
 
 

@@ -54,6 +54,7 @@ class UadGanIO(C.Structure):
 
 ZOOM_CONSTANT, ZOOM_NEAREST = 0, 1
 ZOOM_F32, ZOOM_I32 = 0, 1
+RESIZE_LINEAR, RESIZE_NEAREST = 0, 1
 AFFINE_MAX_K = 16                                                  # include/uad_hip.h: UAD_AFFINE_MAX_K
 SELECT_ALL, SELECT_NONNEG = 0, 1
 SELECT_MAX_Q, SELECT_TILE, HISTOGRAM_MAX_BINS = 4, 8192, 1024      # include/uad_hip.h: UAD_SELECT_MAX_Q, UAD_SELECT_TILE, UAD_HISTOGRAM_MAX_BINS
@@ -137,6 +138,8 @@ SYMBOLS = {
     'uad_curvature_flow_workspace': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'uad_curvature_flow': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    'uad_resize2d': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_mask_by_label': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'uad_select_workspace': (C.c_size_t, [C.c_int]),
     'uad_select_quantiles': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.c_int, C.c_uint, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -202,6 +202,70 @@ class _EvalOps(OrderStatOps):
                                                self._stream()))
         return out
 
+    def resize(self, slices, out_hw, mode='linear', index=None):
+        """cv2.resize(s, (W, H)) of slices of a [n_in,h,w] array / tensor on the device (uad_resize2d; dataloaders/BRAINWEB.py:140-142):
+        mode 'linear' = the default INTER_LINEAR (the image), 'nearest' = INTER_NEAREST (the label map), the arithmetic of utils/resize.py --
+        OpenCV 4.2's resize.cpp written down, not compared with OpenCV's own output -- and its bits.  out_hw = (H, W).  index: None = every
+        slice in order, otherwise the input slice of each output slice (any order, repeats allowed; validated here, on the host), so that the
+        kept slices of a resident slice-major volume are resized where they lie.  -> fp32 device tensor [n,H,W]."""
+        if mode not in ('linear', 'nearest'):
+            raise ValueError(f"resize mode must be 'linear' or 'nearest', got {mode!r}")
+        s = slices if isinstance(slices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(slices, np.float32))
+        s = s.to(self.device, torch.float32).contiguous()
+        if s.dim() != 3 or s.numel() == 0:
+            raise ValueError(f'slices must be a non-empty [n,h,w], got {tuple(s.shape)}')
+        n_in, h, w = s.shape
+        H, W = (int(v) for v in out_hw)
+        if H < 1 or W < 1:
+            raise ValueError(f'out_hw must be positive, got {(H, W)}')
+        idx, n = None, n_in
+        if index is not None:
+            host = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+            if host.size == 0:
+                host = host.astype(np.int64)
+            if host.ndim != 1 or not np.issubdtype(host.dtype, np.integer):
+                raise ValueError(f'index must be a 1-D integer list, got shape {host.shape} dtype {host.dtype}')
+            if host.size and (host.min() < 0 or host.max() >= n_in):
+                raise ValueError(f'index entries must lie in [0, {n_in}), got {int(host.min())} .. {int(host.max())}')
+            n = int(host.size)
+            idx = torch.from_numpy(np.ascontiguousarray(host, np.int32)).to(self.device)
+        out = torch.empty((n, H, W), device=self.device, dtype=torch.float32)
+        if n == 0:
+            return out
+        _lib.check(self.lib.uad_resize2d(_ptr(s), n_in, h, w, _ptr(idx), n, H, W, _lib.RESIZE_NEAREST if mode == 'nearest' else _lib.RESIZE_LINEAR,
+                                         _ptr(out), self._stream()))
+        return out
+
+    def mask_by_label(self, vol, labels, keep, lesion_label=None, out=None):
+        """The skull-map multiply and the lesion binarisation of BRAINWEB.load_volume_and_groundtruth (dataloaders/BRAINWEB.py:266-289) in one
+        device pass (uad_mask_by_label): vol (fp32, any shape) where the uint8 tissue class `labels` is one of `keep`, +0 elsewhere.
+        -> the masked fp32 device tensor, or with lesion_label (masked, lesion) where lesion = 1.0 at labels == lesion_label, else 0.0.
+        out: None = a new tensor; `vol` itself (a device tensor) masks in place."""
+        v = vol if isinstance(vol, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(vol, np.float32))
+        v = v.to(self.device, torch.float32).contiguous()
+        lb = labels if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        if lb.dtype not in (torch.uint8, np.uint8):
+            raise TypeError(f'labels must be uint8, got {lb.dtype}')
+        if not isinstance(lb, torch.Tensor):
+            lb = torch.from_numpy(np.ascontiguousarray(lb))
+        lb = lb.to(self.device).contiguous()
+        if lb.shape != v.shape or v.numel() == 0:
+            raise ValueError(f'vol {tuple(v.shape)} and labels {tuple(lb.shape)} must be non-empty and of one shape')
+        lut = np.zeros(256, np.uint8)
+        keep = [int(k) for k in keep]
+        if any(k < 0 or k > 255 for k in keep) or (lesion_label is not None and not 0 <= int(lesion_label) <= 255):
+            raise ValueError('label values are bytes: 0 .. 255')
+        lut[keep] = 1
+        lut_d = torch.from_numpy(lut).to(self.device)
+        if out is None:
+            out = torch.empty_like(v)
+        elif not (isinstance(out, torch.Tensor) and out.is_contiguous() and out.dtype == torch.float32 and out.shape == v.shape and out.device == v.device):
+            raise ValueError('out must be a contiguous fp32 device tensor of vol\'s shape')
+        lesion = torch.empty_like(v) if lesion_label is not None else None
+        _lib.check(self.lib.uad_mask_by_label(_ptr(v), _ptr(lb), v.numel(), _ptr(lut_d), _ptr(out), _ptr(lesion),
+                                              -1 if lesion_label is None else int(lesion_label), self._stream()))
+        return out if lesion_label is None else (out, lesion)
+
     def mc_stats(self, recs, mask=None):
         """Monte-Carlo dropout statistics (utils/Evaluation.py:238-266): recs [K, ...] device / host array of K reconstructions, mask
         broadcastable to one sample.  Returns (mean, epistemic variance) of the masked reconstructions as device tensors."""

@@ -13,6 +13,10 @@ MSISBI2015.py:231, MSSEG2008.py:241,246) is the keyword `curvature_flow` of `vol
 from its source, and csrc/uad_flow.hip runs the same arithmetic on the device with the same bits.  That statement has not been compared with
 SimpleITK's own output yet, which is why `denoise=True` still raises and the filter has a keyword of its own.
 
+`volume_to_slices(loader='brainweb')` restates the training set's preparation instead (dataloaders/BRAINWEB.py:125-185, 266-292): one
+tissue-class map for the skull map and the lesion map, the constant-slice filter, `cv2.resize` (utils/resize.py; csrc/uad_resize.hip on the
+device) for slices larger than `sliceResolution` and zero padding otherwise.
+
 `build_cache` turns a list of patients into the slice cache of utils/slice_cache.py with the reference's patient-level TRAIN / VAL / TEST
 partition (a permutation of the patients cut at floor(fraction * n), MSLUB.py:71-90)."""
 import gzip
@@ -183,7 +187,8 @@ def crop_center(img, cropx, cropy):
 
 def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0, slice_end=155, slice_resolution=None, skull_stripping=True,
                      view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None,
-                     device_stats=None, device_rotate=None, curvature_flow=None, spacing=(1, 1, 1)):
+                     device_stats=None, device_rotate=None, curvature_flow=None, spacing=(1, 1, 1), loader='mslub', skull_removal=True,
+                     background_removal=True):
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
     map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
@@ -203,8 +208,24 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     scales its differences by (build_cache takes it from the NIfTI header).  The arithmetic is utils/curvature_flow.py's -- ITK's update written
     down from its source, not yet compared with SimpleITK's own output.  With an engine that has the `curvature_flow` op
     (engine._EvalOps.curvature_flow) it runs there, same bits; with device_stats on, the skull-strip multiply and the move to slice-major order
-    happen on the device too, so the volume is uploaded once and not downloaded in between.  Without such an engine: the host statement."""
+    happen on the device too, so the volume is uploaded once and not downloaded in between.  Without such an engine: the host statement.
+    loader: 'mslub' (default) is everything above, the MS datasets' preparation.  'brainweb' is the training set's
+    (dataloaders/BRAINWEB.py:125-185, 266-292; see _brainweb_to_slices): `seg` is the TISSUE-CLASS volume (values 0 .. 10) that supplies both
+    the skull map -- skull_removal drops FAT, MUSCLE, SKIN, SKULL, CONNECTIVE (4, 5, 6, 7, 9), background_removal drops BACKGROUND (0) -- and
+    the lesion map (== 10); constant slices are dropped; a slice larger than slice_resolution on either axis is resized with utils/resize.py
+    (cv2.resize: bilinear image, nearest label), otherwise zero-padded; no spline, no re-threshold.  brainmask must be None and
+    curvature_flow off (the reference does not denoise BrainWeb); skull_stripping, empty_percentile, empty_thresh and device_stats do not
+    apply."""
     from scipy.ndimage import rotate, zoom
+    if loader == 'brainweb':
+        if brainmask is not None:
+            raise ValueError("loader='brainweb' takes no brainmask: the skull map comes from the tissue classes in `seg`")
+        if _flow_setting(curvature_flow) is not None or denoise:
+            raise ValueError("loader='brainweb' does not denoise: the reference calls nii.denoise() for the MS datasets only")
+        return _brainweb_to_slices(vol, seg, axis, slice_start, slice_end, slice_resolution, view_mapping, rotations, center_crop, engine, device_rotate,
+                                   skull_removal, background_removal)
+    if loader != 'mslub':
+        raise ValueError(f"loader must be 'mslub' or 'brainweb', got {loader!r}")
     if denoise:
         raise NotImplementedError("nii.denoise() is SimpleITK's CurvatureFlow filter (MSLUB.py:257); it is not restated here")
     vm = view_mapping or VIEW_MAPPING
@@ -312,6 +333,116 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     return np.stack(imgs), np.stack(labs), kept
 
 
+BRAINWEB_SKULL_CLASSES = (4, 5, 6, 7, 9)      # BRAINWEB.LABELS FAT, MUSCLE, SKIN, SKULL, CONNECTIVE (BRAINWEB.py:273-277)
+BRAINWEB_BACKGROUND, BRAINWEB_LESION = 0, 10
+
+
+def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolution, view_mapping, rotations, center_crop, engine, device_rotate,
+                        skull_removal, background_removal):
+    """volume_to_slices(loader='brainweb'): dataloaders/BRAINWEB.py:125-185 with load_volume_and_groundtruth (:266-292) on the repo's arrays.
+    NaN -> 0; the skull map is 1 except at the dropped tissue classes and multiplies the volume when either flag is set; the lesion map is
+    tissue == 10; normalize_scaling(0, 99.8); then per slice of [slice_start, min(slice_end, n)): a CONSTANT slice (numpy.unique(...).size == 1,
+    :133) is skipped; a slice larger than slice_resolution on either axis is resized -- utils/resize.py's resize_linear for the image,
+    resize_nearest for the label -- and every other slice is zero-padded, centred with `//` starts (:144-154).
+    The output-shape quirk: the reference hands tuple(sliceResolution) to cv2.resize, which reads it as (width, height), so a RESIZED slice
+    has shape (slice_resolution[1], slice_resolution[0]) while a PADDED one has shape slice_resolution.  Restated as it is; only a
+    non-square resolution shows it.
+    A masked voxel is +0 here whatever its sign was (the reference's multiply leaves -0 for a negative one; the two compare equal).
+    With an engine that has the `resize` op the whole path runs on the device: one upload of the slice-major volume (fp32) and of the tissue
+    classes (uint8), engine.mask_by_label, _normalize_scaling_on, the constant-slice filter as ONE select_quantiles call with q = [0, 1] and
+    one segment per slice (constant <=> minimum == maximum: the input is NaN-free and +-0 compare equal there as in numpy.unique),
+    engine.resize(index=kept) or a padded copy for both maps, then _rotate_on or one download.  Same kept slices and the same bits as
+    engine=None; rotated outputs within the fp32 rounding documented for engine.rotate."""
+    from scipy.ndimage import rotate
+    from .resize import resize_linear, resize_nearest
+    ax = (view_mapping or VIEW_MAPPING)[axis]
+    vol = np.array(vol, np.float64)
+    vol[np.isnan(vol)] = 0.0
+    if tissue is None:
+        raise ValueError("loader='brainweb' needs the tissue-class volume as `seg`")
+    tissue_in = np.asarray(tissue)
+    if tissue_in.shape != vol.shape:
+        raise ValueError(f'tissue-class volume {tissue_in.shape} and volume {vol.shape} differ in shape')
+    tissue = tissue_in.astype(np.uint8)
+    if not np.array_equal(tissue, tissue_in):
+        raise ValueError('the tissue-class volume must hold integer class values 0 .. 255')
+    dropped = (BRAINWEB_SKULL_CLASSES if skull_removal else ()) + ((BRAINWEB_BACKGROUND,) if background_removal else ())
+    keep = [c for c in range(256) if c not in dropped]
+    on_device = engine is not None and hasattr(engine, 'resize')
+    if device_rotate is None:
+        device_rotate = hasattr(engine, 'rotate')
+    elif device_rotate and not hasattr(engine, 'rotate'):
+        raise ValueError('device_rotate needs an engine with the rotate op')
+    device_rotate = bool(device_rotate) and any(a != 0 for a in rotations)
+    n = vol.shape[ax]
+    s_end = min(slice_end, n)
+    h, w = np.moveaxis(vol, ax, 0).shape[1:]
+    resized = slice_resolution is not None and (h > slice_resolution[0] or w > slice_resolution[1])      # :140
+    if on_device:
+        import torch
+        moved = engine._dev(np.ascontiguousarray(np.moveaxis(vol, ax, 0), np.float32))
+        masked, lesion = engine.mask_by_label(moved, np.ascontiguousarray(np.moveaxis(tissue, ax, 0)), keep, BRAINWEB_LESION, out=moved)
+        vol_dev = _normalize_scaling_on(engine, masked, 0, 99.8)
+        kept_s = []
+        if s_end > slice_start:
+            _, lo, hi = engine.select_quantiles(vol_dev[slice_start:s_end], [0.0, 1.0], [False, False], segments=s_end - slice_start)
+            kept_s = [slice_start + int(i) for i in np.flatnonzero(~(lo[:, 0] == hi[:, 1]))]           # :133, one segment per slice
+        if not kept_s:
+            return np.zeros((0, 0, 0), np.float32), np.zeros((0, 0, 0), np.float32), []
+        if resized:
+            out_hw = (slice_resolution[1], slice_resolution[0])             # cv2's dsize is (width, height)
+            sds = engine.resize(vol_dev, out_hw, mode='linear', index=kept_s)
+            sss = engine.resize(lesion, out_hw, mode='nearest', index=kept_s)
+        else:
+            sds, sss = vol_dev[kept_s], lesion[kept_s]
+            if slice_resolution is not None:
+                H, W = slice_resolution
+                y0, x0 = (H - h) // 2, (W - w) // 2
+                both = sds.new_zeros((2, len(kept_s), H, W))
+                both[0, :, y0:y0 + h, x0:x0 + w] = sds
+                both[1, :, y0:y0 + h, x0:x0 + w] = sss
+                sds, sss = both[0], both[1]
+        if device_rotate:
+            return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop)
+        both = torch.stack([sds, sss]).cpu().numpy()                        # the one download
+        sds, sss = list(both[0]), list(both[1])
+    else:
+        if dropped:
+            vol = np.where(np.isin(tissue, dropped), 0.0, vol)              # :272-289
+        lesion = (tissue == BRAINWEB_LESION).astype(np.float32)             # :283-286
+        vol = normalize_scaling(vol)                                        # :292
+        sds, sss, kept_s = [], [], []
+        for s in range(slice_start, s_end):
+            idx = [slice(None)] * 3
+            idx[ax] = s
+            sd, ss = vol[tuple(idx)], lesion[tuple(idx)]
+            if np.unique(sd).size == 1:                                     # :133
+                continue
+            if resized:
+                sd = resize_linear(sd, (slice_resolution[1], slice_resolution[0]))
+                ss = resize_nearest(ss, (slice_resolution[1], slice_resolution[0]))
+            elif slice_resolution is not None:
+                H, W = slice_resolution
+                y0, x0 = (H - h) // 2, (W - w) // 2
+                pd, ps = np.zeros((H, W), np.float32), np.zeros((H, W), np.float32)
+                pd[y0:y0 + h, x0:x0 + w] = sd
+                ps[y0:y0 + h, x0:x0 + w] = ss
+                sd, ss = pd, ps
+            sds.append(sd); sss.append(ss); kept_s.append(s)
+        if device_rotate and len(sds):
+            return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop)
+    imgs, labs, kept = [], [], []
+    for sd, ss, s in zip(sds, sss, kept_s):
+        for angle in rotations:
+            sdr, ssr = (sd, ss) if angle == 0 else (rotate(sd, angle, reshape=False), rotate(ss, angle, reshape=False, mode='nearest'))
+            if center_crop is not None:
+                sdr, ssr = crop_center(sdr, center_crop[0], center_crop[1]), crop_center(ssr, center_crop[0], center_crop[1])
+            imgs.append(np.asarray(sdr, np.float32)); labs.append(np.asarray(ssr, np.float32)); kept.append(s)
+    if not imgs:
+        return np.zeros((0, 0, 0), np.float32), np.zeros((0, 0, 0), np.float32), []
+    return np.stack(imgs), np.stack(labs), kept
+
+
 def _flow_setting(curvature_flow):
     """volume_to_slices' `curvature_flow` keyword -> None | (iterations, time_step)."""
     if curvature_flow is None or curvature_flow is False:
@@ -371,7 +502,8 @@ def partition_patients(n_patients, partition=None, rng=None):
 
 def build_cache(directory, patients, partition=None, seed=0, engine=None, **slice_options):
     """patients: [{'name', 'volume': path, 'groundtruth': path or None, 'skullmap': path or None}] -> slice cache in `directory`.
-    slice_options: volume_to_slices keywords (device_stats, curvature_flow among them); engine: volume_to_slices' device resampler / order
+    slice_options: volume_to_slices keywords (device_stats, curvature_flow, loader / skull_removal / background_removal among them; with
+    loader='brainweb' 'groundtruth' names the tissue-class volume and 'skullmap' is ignored); engine: volume_to_slices' device resampler / order
     statistics / curvature flow.  Unless slice_options names a `spacing`, each volume gets its own from its header: abs(pixdim[1:4]), a zero
     replaced by 1.0.
     Returns the index dict that was written."""
@@ -387,7 +519,7 @@ def build_cache(directory, patients, partition=None, seed=0, engine=None, **slic
             continue
         vol, hdr = read_nifti(p['volume'])
         seg = read_nifti(p['groundtruth'])[0] if p.get('groundtruth') else None
-        msk = read_nifti(p['skullmap'])[0] if p.get('skullmap') else None
+        msk = read_nifti(p['skullmap'])[0] if p.get('skullmap') and slice_options.get('loader', 'mslub') != 'brainweb' else None
         spacing = tuple(abs(float(d)) or 1.0 for d in hdr['pixdim'][1:4])
         im, lb, kept = volume_to_slices(vol, seg, msk, engine=engine, **{'spacing': spacing, **slice_options})
         if len(kept):
