@@ -28,6 +28,8 @@
  *       <- utils/NII.py:85-87 (nii.denoise(): sitk.CurvatureFlow, called by dataloaders/MSLUB.py:242 and its siblings)
  *   uad_resize2d / uad_mask_by_label
  *       <- dataloaders/BRAINWEB.py:140-142 (cv2.resize of slices larger than sliceResolution), :266-289 (skull map from the tissue classes)
+ *   uad_cc_props / uad_crop2d
+ *       <- dataloaders/MSLUB.py:200-222 (cropType 'lesions': regionprops centroids, one crop per component), BRAINWEB.py:166-173 ('random')
  *   uad_set_params / uad_get_params / uad_tensor_info
  *       <- tf.global_variables_initializer / tf.train.Saver variable access (trainers/DLMODEL.py:63-110)
  *   uad_op_*  — single-kernel entry points used by the parity tests (no reference counterpart).
@@ -401,6 +403,31 @@ enum { UAD_RESIZE_LINEAR = 0, UAD_RESIZE_NEAREST = 1 };
 int uad_resize2d(const float* in, int n_in, int h, int w, const int* slice_idx, int n, int H, int W, int mode, float* out, void* stream);
 int uad_mask_by_label(const float* vol, const unsigned char* labels, long long n, const unsigned char* lut256, float* out, float* lesion_out,
                       int lesion_label, void* stream);
+
+/* ---- component measurements and crop windows (csrc/uad_crops.hip) <- dataloaders/MSLUB.py:200-222 (MSISBI2015.py / MSSEG2008.py alike),
+ *      dataloaders/BRAINWEB.py:166-173, utils/image_utils.py:15-16 --------------------------------------------------------------
+ * uad_cc_props: the `regionprops` half of cropType 'lesions' (MSLUB.py:201-206: label, regionprops, prop['centroid']) as utils/crops.py's
+ *   component_props states it (skimage is not a dependency; that statement has not been compared with skimage's own output).
+ *   labels: DEVICE int32 [D,H,W], the output of uad_cc_label with any slab (with slab = 1 every slice is labelled on its own: skimage's
+ *   8-connectivity on a 2-D slice).  props: DEVICE int64 [max_components,5], one row per component -- first (its smallest linear index
+ *   (z*H + y)*W + x), area, sum_z, sum_y, sum_x -- ordered by `first`, ascending: slice-major for slab = 1 and regionprops' order inside a
+ *   slice; the centroid is (sum_z, sum_y, sum_x) / area.  *n_components (DEVICE) = the true number of components, also when it exceeds
+ *   max_components: then only the first max_components rows are written and nothing is written past them.
+ *   Roots (labels[v] == v + 1) are counted per tile and ranked in index order by a scan, then every foreground voxel adds to its root's row:
+ *   integers only -- 64-bit LDS atomics per tile, 64-bit global atomics for the rest -- so the result does not depend on the order of
+ *   execution.  Four launches, no host synchronisation.  workspace: device memory of at least uad_cc_props_workspace(D, H, W) bytes (the
+ *   tile counts and one int32 per voxel), 16-byte aligned, owned by the caller, any contents, free once the call's work on `stream` is
+ *   done.  UAD_ERR_INVALID: a non-positive size (the workspace query returns 0), max_components < 1, a NULL pointer, D*H*W >= 2^31.
+ * uad_crop2d: image_utils.crop (img[y:y + height, x:x + width]; MSLUB.py:215-218, BRAINWEB.py:172-173) for k windows at once: out[j] (DEVICE
+ *   fp32 [k,ch,cw]) = the ch x cw window of slice origins[j][0] of in (DEVICE fp32 [n_in,h,w]) with its top-left corner at row origins[j][1],
+ *   column origins[j][2].  origins: DEVICE int32 [k,3] of (slice, top, left), any order, repeats allowed.  The words are copied: +-0,
+ *   denormals and NaN payloads survive.  One launch, no workspace, no atomics; 16-byte stores where cw is a multiple of four and out is
+ *   16-byte aligned.  A slice outside [0, n_in) or a window that leaves the slice is the caller's error (engine.crop validates the origins on
+ *   the host).  UAD_ERR_INVALID: a non-positive size, ch > h or cw > w, a NULL pointer, out aliasing in.  UAD_ERR_UNSUPPORTED: more than one
+ *   grid holds -- k > 65535 windows; split the call. */
+size_t uad_cc_props_workspace(int D, int H, int W);
+int uad_cc_props(const int* labels, int D, int H, int W, long long* props, int max_components, int* n_components, void* workspace, void* stream);
+int uad_crop2d(const float* in, int n_in, int h, int w, const int* origins, int k, int ch, int cw, float* out, void* stream);
 
 /* ---- order statistics without a sort (csrc/uad_select.hip) ----------------------------------------------------
  * uad_select_quantiles: segmented radix select over fp32 `in` [n_seg, n_per_seg] (device, contiguous).  For each segment: m = the number

@@ -18,6 +18,11 @@ as cv2.resize does (bilinear image, nearest label; utils/resize.py, not compared
 one zero-padded.  --no-skull-removal keeps FAT / MUSCLE / SKIN / SKULL / CONNECTIVE, --no-background-removal keeps BACKGROUND.  With a device
 engine (--device-resample or --device-stats) the whole path runs on the GPU (uad_mask_by_label, uad_select_quantiles, uad_resize2d).
 --curvature-flow is refused for this loader: the reference does not denoise BrainWeb.
+--crops {center,lesions,random} W H caches crops instead of whole slices, the reference's `useCrops` with its cropType, cropWidth and cropHeight
+(dataloaders/MSLUB.py:186-222, BRAINWEB.py:165-180; nifti.volume_to_slices(crops=...), utils/crops.py): the centre crop, one crop per lesion
+of the label slice centred on its centroid (not with --rotations), or --random-crops-per-slice N windows per slice whose corners come from a
+numpy RandomState seeded with --crop-seed S (one stream over all patients; the label map is cropped at the image's origins).  With a device
+engine the component measurements and the window gather run on the GPU (uad_cc_label, uad_cc_props, uad_crop2d) -- the same crops bit for bit.
 """
 import argparse
 import json
@@ -49,10 +54,27 @@ def main():
                     help="'brainweb': the training set's preparation; --gt names the tissue-class file, --mask is ignored")
     ap.add_argument('--no-skull-removal', action='store_true', help='--loader brainweb: keep the skull tissue classes (4, 5, 6, 7, 9)')
     ap.add_argument('--no-background-removal', action='store_true', help='--loader brainweb: keep the background class (0)')
+    ap.add_argument('--crops', nargs=3, default=None, metavar=('MODE', 'W', 'H'), help="cache crops of W x H (width, height): MODE center | lesions | random")
+    ap.add_argument('--random-crops-per-slice', type=int, default=5, metavar='N', help='--crops random: windows per slice and angle (numRandomCropsPerSlice)')
+    ap.add_argument('--crop-seed', type=int, default=0, metavar='S', help='--crops random: seed of the numpy RandomState the corners are drawn from')
     a = ap.parse_args()
     if a.curvature_flow is not None and len(a.curvature_flow) not in (0, 2):
         ap.error('--curvature-flow takes no values or ITER STEP')
     flow = None if a.curvature_flow is None else (True if not a.curvature_flow else (int(a.curvature_flow[0]), float(a.curvature_flow[1])))
+    crops = {}
+    if a.crops is not None:
+        if a.crops[0] not in ('center', 'lesions', 'random'):
+            ap.error('--crops MODE must be center, lesions or random')
+        try:
+            w, h = int(a.crops[1]), int(a.crops[2])
+        except ValueError:
+            ap.error('--crops W H must be integers')
+        if a.crops[0] == 'lesions' and any(r != 0 for r in a.rotations):
+            ap.error('--crops lesions does not go with --rotations')
+        crops = {'crops': (a.crops[0], w, h)}
+        if a.crops[0] == 'random':
+            import numpy as np
+            crops = {'crops': ('random', w, h, a.random_crops_per_slice), 'rng': np.random.RandomState(a.crop_seed)}
     patients = []
     for name in sorted(os.listdir(a.root)):
         d = os.path.join(a.root, name)
@@ -77,7 +99,7 @@ def main():
     info = nifti.build_cache(a.cache, patients, partition={'TRAIN': a.train, 'VAL': a.val, 'TEST': a.test}, seed=a.seed, engine=engine, axis=a.axis,
                              slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'rotations': tuple(a.rotations)} if list(a.rotations) != [0] else {}),
                              **({'device_stats': a.device_stats} if engine is not None and not loader else {}), **({'curvature_flow': flow} if flow is not None else {}),
-                             **loader)
+                             **loader, **crops)
     print(json.dumps(info))
 
 

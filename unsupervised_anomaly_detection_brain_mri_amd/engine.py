@@ -320,6 +320,72 @@ class _EvalOps(OrderStatOps):
         tps, fps, fns = (int(c) for c in counts.cpu().tolist())
         return tps, fps, fns
 
+    def region_props(self, volume_or_labels, slab=0):
+        """skimage's label + regionprops as dataloaders/MSLUB.py:201-206 use them, on the device (uad_cc_label + uad_cc_props; the statement is
+        utils/crops.py's component_props -- skimage is not a dependency and has not been compared with): a [D,H,W] volume -> host int64 array
+        [K,5], one row per 26-connected component: first (smallest linear index), area, sum_z, sum_y, sum_x, ordered by `first`.
+        An int32 array / tensor is taken as a LABEL volume (the output of cc_label; `slab` is then the labelling's and is not used here);
+        anything else is a mask (non-zero = foreground) and is labelled first in groups of `slab` slices (1: every slice on its own, the
+        8-connectivity of a 2-D slice).  The count comes from the labelling (one small synchronising download), after which the table is
+        allocated exactly; for a label volume a table of 4096 rows is tried first."""
+        v = volume_or_labels
+        is_labels = (v.dtype == torch.int32) if isinstance(v, torch.Tensor) else (np.asarray(v).dtype == np.int32)
+        count = None
+        if is_labels:
+            lab = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(self.device).contiguous()
+            if lab.dim() != 3:
+                raise ValueError('region_props expects a [D,H,W] volume')
+        else:
+            m = self._binary_volume(v, 'region_props')
+            if m.numel() == 0:
+                raise ValueError('region_props expects a non-empty volume')
+            lab = torch.empty(m.shape, device=self.device, dtype=torch.int32)
+            cnt = torch.empty(1, device=self.device, dtype=torch.int32)
+            _lib.check(self.lib.uad_cc_label(_ptr(m), m.shape[0], m.shape[1], m.shape[2], int(slab), _ptr(lab), _ptr(cnt), self._stream()))
+            count = int(cnt.item())
+            if count == 0:
+                return np.zeros((0, 5), np.int64)
+        D, H, W = lab.shape
+        nbytes = int(self.lib.uad_cc_props_workspace(D, H, W))
+        if nbytes == 0:
+            raise ValueError(f'region_props: a volume of {D} x {H} x {W} is empty or has 2^31 voxels or more')
+        ws = torch.empty((nbytes + 7) // 8, device=self.device, dtype=torch.int64)          # stream-ordered caching allocator: safe to drop after the launches
+        n_dev = torch.empty(1, device=self.device, dtype=torch.int32)
+        cap = count if count is not None else 4096
+        while True:
+            props = torch.empty((cap, 5), device=self.device, dtype=torch.int64)
+            _lib.check(self.lib.uad_cc_props(_ptr(lab), D, H, W, _ptr(props), cap, _ptr(n_dev), _ptr(ws), self._stream()))
+            n = int(n_dev.item())
+            if n <= cap:
+                return props[:n].cpu().numpy()
+            cap = n
+
+    def crop(self, slices, origins, crop_hw):
+        """image_utils.crop (img[y:y + height, x:x + width]; dataloaders/MSLUB.py:215-218, BRAINWEB.py:172-173) for k windows of a [n,h,w]
+        array / tensor in one device pass (uad_crop2d).  origins: HOST integer array [k,3] of (slice, top, left), any order, repeats allowed,
+        validated here: the slice in range and the window inside it.  crop_hw = (height, width).  -> fp32 device tensor [k,height,width];
+        the words are copied (+-0, denormals and NaN payloads survive).  k = 0 gives an empty tensor without a launch."""
+        from .utils.crops import check_origins
+        s = slices if isinstance(slices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(slices, np.float32))
+        s = s.to(self.device, torch.float32).contiguous()
+        if s.dim() != 3 or s.numel() == 0:
+            raise ValueError(f'slices must be a non-empty [n,h,w], got {tuple(s.shape)}')
+        n_in, h, w = s.shape
+        ch, cw = (int(v) for v in crop_hw)
+        if ch < 1 or cw < 1 or ch > h or cw > w:
+            raise ValueError(f'crop_hw {(ch, cw)} must be positive and fit the {h} x {w} slice')
+        host = np.asarray(origins.cpu() if isinstance(origins, torch.Tensor) else origins)
+        o = check_origins(host, n_in, h, w, ch, cw)
+        k = int(o.shape[0])
+        out = torch.empty((k, ch, cw), device=self.device, dtype=torch.float32)
+        if k == 0:
+            return out
+        od = torch.from_numpy(np.ascontiguousarray(o)).to(self.device)
+        for j0 in range(0, k, 65535):                                       # one grid holds 65535 windows
+            kk = min(65535, k - j0)
+            _lib.check(self.lib.uad_crop2d(_ptr(s), n_in, h, w, _ptr(od[j0:j0 + kk]), kk, ch, cw, _ptr(out[j0:j0 + kk]), self._stream()))
+        return out
+
     # ---------------------------------------------------------------- order statistics (csrc/uad_select.hip)
     def _f32_exact(self, values):
         """-> contiguous fp32 device tensor of a float32 / float64 array or tensor; ValueError when a float64 value is not a float32 number."""

@@ -17,6 +17,9 @@ SimpleITK's own output yet, which is why `denoise=True` still raises and the fil
 tissue-class map for the skull map and the lesion map, the constant-slice filter, `cv2.resize` (utils/resize.py; csrc/uad_resize.hip on the
 device) for slices larger than `sliceResolution` and zero padding otherwise.
 
+`volume_to_slices(crops=...)` adds the reference's crop modes (`useCrops`: cropType 'center' | 'lesions' | 'random'; MSLUB.py:186-222,
+BRAINWEB.py:165-180): utils/crops.py states the component measurements and the window arithmetic, csrc/uad_crops.hip runs them on the device.
+
 `build_cache` turns a list of patients into the slice cache of utils/slice_cache.py with the reference's patient-level TRAIN / VAL / TEST
 partition (a permutation of the patients cut at floor(fraction * n), MSLUB.py:71-90)."""
 import gzip
@@ -188,7 +191,7 @@ def crop_center(img, cropx, cropy):
 def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0, slice_end=155, slice_resolution=None, skull_stripping=True,
                      view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None,
                      device_stats=None, device_rotate=None, curvature_flow=None, spacing=(1, 1, 1), loader='mslub', skull_removal=True,
-                     background_removal=True):
+                     background_removal=True, crops=None, rng=None):
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
     map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
@@ -215,7 +218,98 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     the lesion map (== 10); constant slices are dropped; a slice larger than slice_resolution on either axis is resized with utils/resize.py
     (cv2.resize: bilinear image, nearest label), otherwise zero-padded; no spline, no re-threshold.  brainmask must be None and
     curvature_flow off (the reference does not denoise BrainWeb); skull_stripping, empty_percentile, empty_thresh and device_stats do not
-    apply."""
+    apply.
+    crops: None | ('center', w, h) | ('lesions', w, h) | ('random', w, h, per_slice): the reference's `useCrops` with its cropType, cropWidth,
+    cropHeight and numRandomCropsPerSlice (MSLUB.py:186-222, BRAINWEB.py:165-180), applied to every prepared (and rotated) slice; utils/crops.py
+    states the arithmetic.  ('center', w, h) IS center_crop=(w, h); giving both raises ValueError.  'lesions': one crop per 8-connected
+    component of the label slice, centred on its centroid, the centre clamped into the slice, a window that still leaves the slice dropped
+    (MSLUB.py:200-222); a non-zero rotation raises ValueError -- the MS loaders have no rotations and a spline-rotated label map is not
+    binary; loader='brainweb' is allowed (its lesion map is binary).  'random': per slice and angle per_slice windows whose corners are
+    drawn from `rng` -- a numpy.random.RandomState, default the numpy.random module as in the reference -- by randint(0, W - w) and
+    randint(0, H - h) (BRAINWEB.py:167-170).  The image crop and the label crop share their origins; the reference appends the IMAGE crop
+    as the label (BRAINWEB.py:173), here the label map is cropped: a stated deviation.
+    Output order: slice-major, angle-minor, then the crops of that slice and angle in origin order (components in raster order of their first
+    pixel; random crops in draw order); `kept` carries the slice index of every crop.
+    With an engine that has `region_props` and `crop` (engine._EvalOps) the prepared image batch and label batch stay on the device, the
+    labels go through region_props(slab=1), the origins are formed on the host from the small table, one crop call serves the images and
+    one the labels, and one download follows.  Without such an engine: the host statement.  The same crops bit for bit."""
+    spec = _crop_setting(crops, center_crop, rotations)
+    if spec is not None and spec[0] == 'center':
+        center_crop, spec = (spec[1], spec[2]), None
+    on_device = spec is not None and hasattr(engine, 'region_props') and hasattr(engine, 'crop')
+    out = _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_resolution, skull_stripping, view_mapping, empty_percentile, empty_thresh,
+                           denoise, rotations, center_crop, engine, device_stats, device_rotate, curvature_flow, spacing, loader, skull_removal, background_removal,
+                           resident=on_device)
+    if spec is None:
+        return out
+    return _crop_slices(out[0], out[1], out[2], spec, rng, engine if on_device else None)
+
+
+def _is_tensor(a):
+    return hasattr(a, 'data_ptr')
+
+
+def _crop_setting(crops, center_crop, rotations):
+    """volume_to_slices' `crops` keyword -> None | (mode, w, h[, per_slice]), validated."""
+    if crops is None:
+        return None
+    try:
+        mode, w, h = crops[0], int(crops[1]), int(crops[2])
+        per = int(crops[3]) if mode == 'random' else None
+        if len(crops) != (4 if mode == 'random' else 3):
+            raise IndexError
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"crops must be ('center', w, h), ('lesions', w, h) or ('random', w, h, per_slice), got {crops!r}") from None
+    if mode not in ('center', 'lesions', 'random'):
+        raise ValueError(f"crops: the mode must be 'center', 'lesions' or 'random', got {mode!r}")
+    if w < 1 or h < 1 or (per is not None and per < 1):
+        raise ValueError(f'crops: sizes and the number of crops per slice must be positive, got {crops!r}')
+    if center_crop is not None:
+        raise ValueError("give either center_crop or crops, not both (crops=('center', w, h) is center_crop=(w, h))")
+    if mode == 'lesions' and any(a != 0 for a in rotations):
+        raise ValueError("crops 'lesions' does not go with rotations: the MS loaders have none, and a spline-rotated label map is not binary")
+    return (mode, w, h) if per is None else (mode, w, h, per)
+
+
+def _crop_slices(images, labels, kept, spec, rng, engine):
+    """The crop step of volume_to_slices for 'lesions' / 'random' on the prepared batches (host arrays, or device tensors with `engine`)."""
+    from .crops import component_props, crop_windows, lesion_crop_origins, random_crop_origins
+    cw, ch = spec[1], spec[2]
+    if not len(kept):
+        return np.zeros((0, ch, cw), np.float32), np.zeros((0, ch, cw), np.float32), []
+    H, W = (int(v) for v in images.shape[-2:])
+    if spec[0] == 'lesions':
+        props = engine.region_props(labels, slab=1) if engine is not None else component_props(labels, slab=1)
+        origins = lesion_crop_origins(props, H, W, cw, ch)
+    else:
+        origins = random_crop_origins(len(kept), H, W, cw, ch, spec[3], rng)
+    if engine is not None:
+        import torch
+        both = torch.stack([engine.crop(images, origins, (ch, cw)), engine.crop(labels, origins, (ch, cw))]).cpu().numpy()      # the one download
+        im, lb = both[0], both[1]
+    else:
+        im, lb = crop_windows(np.asarray(images, np.float32), origins, ch, cw), crop_windows(np.asarray(labels, np.float32), origins, ch, cw)
+    return im, lb, [kept[int(i)] for i in origins[:, 0]]
+
+
+def _resident_result(sds, sss, kept_s, rotations):
+    """The prepared batches as they are (device tensors stay on the device), one entry per slice and angle: only reached without a non-zero
+    angle, so an angle's entry is the slice itself."""
+    R = len(rotations)
+    out = []
+    for b in (sds, sss):
+        if _is_tensor(b):
+            out.append(b.repeat_interleave(R, dim=0) if R != 1 else b)
+        else:
+            b = np.asarray(np.stack(b), np.float32)
+            out.append(np.repeat(b, R, axis=0) if R != 1 else b)
+    return out[0], out[1], [s for s in kept_s for _ in rotations]
+
+
+def _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_resolution, skull_stripping, view_mapping, empty_percentile, empty_thresh, denoise,
+                     rotations, center_crop, engine, device_stats, device_rotate, curvature_flow, spacing, loader, skull_removal, background_removal, resident=False):
+    """volume_to_slices up to and including rotations and center_crop.  resident: leave batches that are on the device there (device tensors
+    [k,H,W] come back in the place of host arrays) when no host step is left to do, i.e. unless a non-zero angle has to be rotated on the host."""
     from scipy.ndimage import rotate, zoom
     if loader == 'brainweb':
         if brainmask is not None:
@@ -223,7 +317,7 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
         if _flow_setting(curvature_flow) is not None or denoise:
             raise ValueError("loader='brainweb' does not denoise: the reference calls nii.denoise() for the MS datasets only")
         return _brainweb_to_slices(vol, seg, axis, slice_start, slice_end, slice_resolution, view_mapping, rotations, center_crop, engine, device_rotate,
-                                   skull_removal, background_removal)
+                                   skull_removal, background_removal, resident)
     if loader != 'mslub':
         raise ValueError(f"loader must be 'mslub' or 'brainweb', got {loader!r}")
     if denoise:
@@ -260,6 +354,7 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     elif device_rotate and not hasattr(engine, 'rotate'):
         raise ValueError('device_rotate needs an engine with the rotate op')
     device_rotate = bool(device_rotate) and any(a != 0 for a in rotations)
+    resident = resident and (device_rotate or not any(a != 0 for a in rotations))
     vol_dev = keep_dev = None
     if device_stats:
         if flow_dev is not None:                                            # the host lines below, on the resident filtered volume
@@ -311,16 +406,18 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
         hw = tuple(int(round(i * f)) for i in sds[0].shape)                 # scipy.ndimage.zoom's output shape
         sds = engine.zoom(sds if device_stats else np.stack(sds), hw, mode='constant')
         sss = engine.zoom(np.stack(sss), hw, mode='nearest')
-        if device_rotate:
+        if device_rotate or resident:
             import torch
             sss = (sss.to(torch.float64) >= 0.9).to(torch.float32)          # the host line below, on the resident batch
         else:
             sds = list(sds.cpu().numpy())
             sss = list((sss.cpu().numpy().astype(np.float64) >= 0.9).astype(np.float64))
-    elif device_stats and len(sds) and not device_rotate:
+    elif device_stats and len(sds) and not device_rotate and not resident:
         sds = list(sds.cpu().numpy())
     if device_rotate and len(sds):
-        return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop)
+        return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop, resident)
+    if resident and len(sds) and center_crop is None:
+        return _resident_result(sds, sss, kept_s, rotations)
     imgs, labs, kept = [], [], []
     for sd, ss, s in zip(sds, sss, kept_s):
         for angle in rotations:
@@ -338,7 +435,7 @@ BRAINWEB_BACKGROUND, BRAINWEB_LESION = 0, 10
 
 
 def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolution, view_mapping, rotations, center_crop, engine, device_rotate,
-                        skull_removal, background_removal):
+                        skull_removal, background_removal, resident=False):
     """volume_to_slices(loader='brainweb'): dataloaders/BRAINWEB.py:125-185 with load_volume_and_groundtruth (:266-292) on the repo's arrays.
     NaN -> 0; the skull map is 1 except at the dropped tissue classes and multiplies the volume when either flag is set; the lesion map is
     tissue == 10; normalize_scaling(0, 99.8); then per slice of [slice_start, min(slice_end, n)): a CONSTANT slice (numpy.unique(...).size == 1,
@@ -374,6 +471,7 @@ def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolut
     elif device_rotate and not hasattr(engine, 'rotate'):
         raise ValueError('device_rotate needs an engine with the rotate op')
     device_rotate = bool(device_rotate) and any(a != 0 for a in rotations)
+    resident = resident and (device_rotate or not any(a != 0 for a in rotations))
     n = vol.shape[ax]
     s_end = min(slice_end, n)
     h, w = np.moveaxis(vol, ax, 0).shape[1:]
@@ -403,7 +501,9 @@ def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolut
                 both[1, :, y0:y0 + h, x0:x0 + w] = sss
                 sds, sss = both[0], both[1]
         if device_rotate:
-            return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop)
+            return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop, resident)
+        if resident and center_crop is None:
+            return _resident_result(sds, sss, kept_s, rotations)
         both = torch.stack([sds, sss]).cpu().numpy()                        # the one download
         sds, sss = list(both[0]), list(both[1])
     else:
@@ -430,7 +530,7 @@ def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolut
                 sd, ss = pd, ps
             sds.append(sd); sss.append(ss); kept_s.append(s)
         if device_rotate and len(sds):
-            return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop)
+            return _rotate_on(engine, sds, sss, kept_s, rotations, center_crop, resident)
     imgs, labs, kept = [], [], []
     for sd, ss, s in zip(sds, sss, kept_s):
         for angle in rotations:
@@ -458,9 +558,10 @@ def _flow_setting(curvature_flow):
     return int(iterations), float(time_step)
 
 
-def _rotate_on(engine, images, labels, kept_s, rotations, center_crop):
+def _rotate_on(engine, images, labels, kept_s, rotations, center_crop, resident=False):
     """volume_to_slices' rotation step on the device: images / labels [k,H,W] (device tensors, or host arrays where no device step came before)
-    -> the (images, labels, kept) volume_to_slices returns.  engine.rotate takes up to 16 angles a call."""
+    -> the (images, labels, kept) volume_to_slices returns.  engine.rotate takes up to 16 angles a call.  resident: no download, the two
+    [k * angles, H, W] batches come back as device tensors (for the crop step)."""
     import torch
     angles = [a for a in rotations if a != 0]
     out = []
@@ -481,6 +582,9 @@ def _rotate_on(engine, images, labels, kept_s, rotations, center_crop):
         y, x = both.shape[-2:]
         sx, sy = x // 2 - center_crop[0] // 2, y // 2 - center_crop[1] // 2
         both = both[..., sy:sy + center_crop[1], sx:sx + center_crop[0]]
+    if resident:
+        both = both.contiguous().reshape(2, -1, both.shape[-2], both.shape[-1])
+        return both[0], both[1], [s for s in kept_s for _ in rotations]
     both = both.contiguous().cpu().numpy()                                            # the one download
     both = both.reshape(2, -1, both.shape[-2], both.shape[-1])              # slice-major, angle-minor
     return both[0], both[1], [s for s in kept_s for _ in rotations]
@@ -502,7 +606,8 @@ def partition_patients(n_patients, partition=None, rng=None):
 
 def build_cache(directory, patients, partition=None, seed=0, engine=None, **slice_options):
     """patients: [{'name', 'volume': path, 'groundtruth': path or None, 'skullmap': path or None}] -> slice cache in `directory`.
-    slice_options: volume_to_slices keywords (device_stats, curvature_flow, loader / skull_removal / background_removal among them; with
+    slice_options: volume_to_slices keywords (device_stats, curvature_flow, loader / skull_removal / background_removal, crops / rng among them: one
+    `rng` serves all patients in order, and it is not recorded in the cache's options; with
     loader='brainweb' 'groundtruth' names the tissue-class volume and 'skullmap' is ignored); engine: volume_to_slices' device resampler / order
     statistics / curvature flow.  Unless slice_options names a `spacing`, each volume gets its own from its header: abs(pixdim[1:4]), a zero
     replaced by 1.0.
@@ -532,5 +637,5 @@ def build_cache(directory, patients, partition=None, seed=0, engine=None, **slic
     # (non-zero after skull stripping), 0 = BACKGROUND
     lab_u8 = np.where(labels > 0, 10, np.where(images[..., 0] > 0, 2, 0)).astype(np.uint8)
     write_cache(directory, images, sets, lab_u8, patients=owner,
-                options={k: (list(v) if isinstance(v, tuple) else v) for k, v in slice_options.items()})
+                options={k: (list(v) if isinstance(v, tuple) else v) for k, v in slice_options.items() if k != 'rng'})
     return {'slices': int(images.shape[0]), 'shape': list(images.shape), 'split': {k: [int(i) for i in v] for k, v in split.items()}}
