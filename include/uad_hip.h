@@ -30,6 +30,9 @@
  *       <- dataloaders/BRAINWEB.py:140-142 (cv2.resize of slices larger than sliceResolution), :266-289 (skull map from the tissue classes)
  *   uad_cc_props / uad_crop2d
  *       <- dataloaders/MSLUB.py:200-222 (cropType 'lesions': regionprops centroids, one crop per component), BRAINWEB.py:166-173 ('random')
+ *   uad_render_minmax_u8 / uad_render_heatmap / uad_render_overlay
+ *       <- utils/Evaluation.py:302-321 (the per-slice PNGs: normalize_and_squeeze :368, squash_intensities + add_colorbar + utils.apply_colormap),
+ *          :501-507 with utils/image_utils.py:22-45 (the TP / FP / FN overlay)
  *   uad_set_params / uad_get_params / uad_tensor_info
  *       <- tf.global_variables_initializer / tf.train.Saver variable access (trainers/DLMODEL.py:63-110)
  *   uad_op_*  — single-kernel entry points used by the parity tests (no reference counterpart).
@@ -43,6 +46,7 @@
 #define UAD_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -428,6 +432,30 @@ int uad_mask_by_label(const float* vol, const unsigned char* labels, long long n
 size_t uad_cc_props_workspace(int D, int H, int W);
 int uad_cc_props(const int* labels, int D, int H, int W, long long* props, int max_components, int* n_components, void* workspace, void* stream);
 int uad_crop2d(const float* in, int n_in, int h, int w, const int* origins, int k, int ch, int cw, float* out, void* stream);
+
+/* ---- 8-bit rendering of the evaluation sample images (csrc/uad_render.hip) <- utils/Evaluation.py:302-321, 368, 501-507,
+ *      utils/image_utils.py:22-45, utils/utils.py:21-26 ---------------------------------------------------------------------------
+ * The arithmetic is utils/render.py's, operation for operation, and the result equals that statement's bit for bit (the heat map up to the
+ * last place of exp()).  Inputs are finite; what a NaN gives is unspecified.  One launch each, no workspace, no atomics, no host
+ * synchronisation; a slice's bytes depend on neither n nor its place in the batch.
+ * uad_render_minmax_u8: normalize_and_squeeze (:368) = cv2.normalize(x, None, 0, 255, NORM_MINMAX) + astype('uint8') of every [hw] slice as
+ *   the statement restates OpenCV's documented arithmetic (it has not been compared with OpenCV's own output, which may fuse the
+ *   multiply-add): smin, smax in fp32; in fp64 scale = smax - smin > DBL_EPSILON ? 255 / (smax - smin) : 0, shift = -smin * scale; per pixel
+ *   in fp32 v = fl(fl(x * (float)scale) + (float)shift); the byte is v truncated toward zero, clamped to 0 .. 255.  A constant slice gives
+ *   zeros.  x: DEVICE fp32 [n,hw]; out: DEVICE u8 [n,hw].
+ * uad_render_heatmap: `_heatmap.png` (:319-321) of every [h,w] slice of d: in fp64 q = 2 * (1 / (1 + exp(-100 d)) - 0.5), the colour bar
+ *   q[i][w-1] = i / h, q -= min q, q /= max q unless that is 0, index = min((int)(q * 256), 255), out = lut256x4[index].  d: DEVICE fp32
+ *   [n,h,w]; lut256x4: DEVICE u8 [256,4] (any table; the jet table is data of the package); out_rgba: DEVICE u8 [n,h,w,4], 4-byte aligned.
+ * uad_render_overlay: augment_prediction_and_groundtruth_to_image (image_utils.py:22-45): grey max(x, 0) on three channels; where pred != 0
+ *   or gt != 0 the colour of TP (0, 1, 0), FP (1, 0.5, 0) or FN (1, 0, 0); the bytes are (uint8)(clip(v, 0, 1) * 255) in fp32, truncated
+ *   (0.5 -> 127).  Stated deviation: the reference's cv2.normalize(tmp, None, 0, 255) with the default norm type and alpha = 0 scales every
+ *   image to zero.  x, pred: DEVICE fp32 [n,hw]; gt: DEVICE u8 [n,hw]; out_rgb: DEVICE u8 [n,hw,3].
+ * One workgroup renders a slice of the two normalising ops: up to 256 x 256 pixels (heat map: 128 x 128) the slice is read once and kept in
+ * registers between the reduction and the map, larger slices are read twice.  n == 0: UAD_OK, nothing is launched.  UAD_ERR_INVALID: n < 0, a non-positive
+ * size, a NULL pointer, out aliasing an input, out_rgba not 4-byte aligned.  UAD_ERR_UNSUPPORTED: a slice of more than 2^31 - 5 pixels. */
+int uad_render_minmax_u8(const float* x, int n, int hw, uint8_t* out, void* stream);
+int uad_render_heatmap(const float* d, int n, int h, int w, const uint8_t* lut256x4, uint8_t* out_rgba, void* stream);
+int uad_render_overlay(const float* x, const float* pred, const uint8_t* gt, int n, int hw, uint8_t* out_rgb, void* stream);
 
 /* ---- order statistics without a sort (csrc/uad_select.hip) ----------------------------------------------------
  * uad_select_quantiles: segmented radix select over fp32 `in` [n_seg, n_per_seg] (device, contiguous).  For each segment: m = the number

@@ -143,6 +143,9 @@ SYMBOLS = {
     'uad_cc_props_workspace': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'uad_cc_props': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'uad_crop2d': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_render_minmax_u8': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_render_heatmap': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_render_overlay': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'uad_select_workspace': (C.c_size_t, [C.c_int]),
     'uad_select_quantiles': (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.c_int, C.c_uint, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),

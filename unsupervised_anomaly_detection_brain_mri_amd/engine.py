@@ -386,6 +386,65 @@ class _EvalOps(OrderStatOps):
             _lib.check(self.lib.uad_crop2d(_ptr(s), n_in, h, w, _ptr(od[j0:j0 + kk]), kk, ch, cw, _ptr(out[j0:j0 + kk]), self._stream()))
         return out
 
+    # ---------------------------------------------------------------- 8-bit rendering of the sample images (csrc/uad_render.hip)
+    def _f32_batch(self, a, what, shape=None):
+        """-> contiguous fp32 device tensor [n,h,w] of an array / tensor (a trailing channel axis of 1 is dropped)."""
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.float32))
+        t = t.to(self.device, torch.float32)
+        if t.dim() == 4 and t.shape[3] == 1:
+            t = t[..., 0]
+        if t.dim() != 3 or t.shape[1] < 1 or t.shape[2] < 1 or (shape is not None and tuple(t.shape) != tuple(shape)):
+            raise ValueError(f'{what} must be [n,h,w] with h, w >= 1' + (f' of shape {tuple(shape)}' if shape is not None else '') + f', got {tuple(t.shape)}')
+        return t.contiguous()
+
+    def render_gray(self, x):
+        """normalize_and_squeeze (utils/Evaluation.py:368: cv2.normalize(x, None, 0, 255, NORM_MINMAX), astype('uint8')) of every slice of a
+        [n,h,w] array / tensor on the device (uad_render_minmax_u8) -> uint8 device tensor [n,h,w] with the bytes of utils/render.py's
+        minmax_u8 -- OpenCV's documented arithmetic written down, not compared with OpenCV's own output.  Integer label maps are cast to
+        fp32 (label_u8)."""
+        t = self._f32_batch(x, 'x')
+        out = torch.empty(tuple(t.shape), device=self.device, dtype=torch.uint8)
+        _lib.check(self.lib.uad_render_minmax_u8(_ptr(t), t.shape[0], t.shape[1] * t.shape[2], _ptr(out), self._stream()))
+        return out
+
+    def render_heatmap(self, d, lut=None):
+        """The squashed heat map with its colour bar (utils/Evaluation.py:319-321) of every slice of a [n,h,w] residual array / tensor on the
+        device (uad_render_heatmap) -> uint8 device tensor [n,h,w,4], the bytes of utils/render.py's heatmap_rgba up to the last place of
+        exp().  lut: a [256,4] uint8 colour table (array or tensor); None = the package's jet table."""
+        from .utils import render
+        t = self._f32_batch(d, 'd')
+        if lut is None:
+            if getattr(self, '_jet_lut', None) is None:
+                self._jet_lut = torch.from_numpy(render.jet_u8().copy()).to(self.device)
+            lut_d = self._jet_lut
+        else:
+            lut_d = lut if isinstance(lut, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(lut))
+            if lut_d.dtype != torch.uint8 or tuple(lut_d.shape) != (256, 4):
+                raise ValueError(f'lut must be [256,4] uint8, got {tuple(lut_d.shape)} {lut_d.dtype}')
+            lut_d = lut_d.to(self.device).contiguous()
+        out = torch.empty(tuple(t.shape) + (4,), device=self.device, dtype=torch.uint8)
+        _lib.check(self.lib.uad_render_heatmap(_ptr(t), t.shape[0], t.shape[1], t.shape[2], _ptr(lut_d), _ptr(out), self._stream()))
+        return out
+
+    def render_overlay(self, x, pred, gt):
+        """image_utils.augment_prediction_and_groundtruth_to_image (utils/Evaluation.py:501-507) for a [n,h,w] batch on the device
+        (uad_render_overlay): x the image, pred the thresholded prediction (non-zero = set), gt the label map (non-zero = set) -> uint8 device
+        tensor [n,h,w,3] with the bytes of utils/render.py's overlay_rgb (not the reference's all-black cv2.normalize call: a stated
+        deviation)."""
+        t = self._f32_batch(x, 'x')
+        p = pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(pred) != 0, np.float32))
+        p = self._f32_batch(p, 'pred', t.shape)
+        g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(gt) != 0, np.uint8))
+        g = (g.to(self.device) != 0).to(torch.uint8)
+        if g.dim() == 4 and g.shape[3] == 1:
+            g = g[..., 0]
+        if tuple(g.shape) != tuple(t.shape):
+            raise ValueError(f'gt must have the shape of x {tuple(t.shape)}, got {tuple(g.shape)}')
+        g = g.contiguous()
+        out = torch.empty(tuple(t.shape) + (3,), device=self.device, dtype=torch.uint8)
+        _lib.check(self.lib.uad_render_overlay(_ptr(t), _ptr(p), _ptr(g), t.shape[0], t.shape[1] * t.shape[2], _ptr(out), self._stream()))
+        return out
+
     # ---------------------------------------------------------------- order statistics (csrc/uad_select.hip)
     def _f32_exact(self, values):
         """-> contiguous fp32 device tensor of a float32 / float64 array or tensor; ValueError when a float64 value is not a float32 number."""

@@ -2,7 +2,8 @@
 description)` (:372-526), `_evaluate(datasetObj, modelObj, sampleDir, options, split)` (:183-365) and
 `determine_threshold_on_labeled_patients(dataset_pc, model, options, epoch, description)` (:529-570) on the dataset duck-type
 (`patients`, `get_patient_idx`, `load_volume_and_groundtruth`, `options.{sliceStart, sliceEnd, axis, sliceResolution}`), over the
-array-level core `evaluate_arrays` / `evaluate_volume` (PNG / PDF export dropped; options['exportVolumes'] writes the NIfTI volumes).  Everything between the reconstruction and the scalar metrics stays on the device:
+array-level core `evaluate_arrays` / `evaluate_volume` (options['exportVolumes'] writes the NIfTI volumes, options['exportSamples'] the per-slice
+PNG images of samples_test_PC/, rendered to 8 bits on the device: export_patient_samples / export_overlays; the PDF / CSV histograms are dropped).  Everything between the reconstruction and the scalar metrics stays on the device:
 slices of a volume are reconstructed in ONE batched call (the reference runs one sess.run per slice, :246-250), the brain
 masks are eroded (uad_erode_cross), residual map + mask + hyper-intensity prior come from uad_residual, the 5x5x5 median is
 uad_median3d, and AUROC / AUPRC / the Dice threshold sweep read one device sort of all voxels (uad_scores_*).
@@ -160,11 +161,14 @@ def _best_dice_of(model, diffs, labels):
     return best
 
 
-def evaluate_volume(model, volume, brainmasks, options, eps=None, device_out=False, prior=None):
+def evaluate_volume(model, volume, brainmasks, options, eps=None, device_out=False, prior=None, collector=None):
     """volume [S,H,W] in [0,1]; brainmasks [S,H,W].  Returns the post-processed residual sub-volume [S,H,W] (numpy, or the
     device tensor with device_out=True) and per-slice l1 reconstruction errors (utils/Evaluation.py:223-312).
     eps: None = z is sampled as the reference's graph does at evaluation too; 0.0 = the deterministic mode.
-    prior: the hyper-intensity threshold (the reference takes the 0.9 quantile of the WHOLE loaded volume, :207); default: of `volume`."""
+    prior: the hyper-intensity threshold (the reference takes the 0.9 quantile of the WHOLE loaded volume, :207); default: of `volume`.
+    collector: None, or a dict that receives what the sample images need beyond the result, kept on the device: 'reconstructions' [S,H,W] (the
+    batch reconstructions; with Monte-Carlo dropout their brain-masked mean, :280-281) and 'residual' [S,H,W], the residual volume before the
+    5x5x5 median (:305 `_diff.png`)."""
     S = volume.shape[0]
     eng = model.engine
     if not should(options, 'applyHyperIntensityPrior'):
@@ -192,12 +196,18 @@ def evaluate_volume(model, volume, brainmasks, options, eps=None, device_out=Fal
             var[s0:s0 + bs] = v[..., 0]
         else:
             rec = model.reconstruct(xb, eps=eps, **rkw)['reconstruction']
+        if collector is not None:
+            rec = eng._dev(rec)                            # uploaded once: the residual op and the collector share the device copy
+            collector.setdefault('_recs', []).append(rec.reshape((-1,) + tuple(volume.shape[1:])))
         d, e = eng.residual(xb, rec, masks[s0:s0 + bs, ..., None], pos_only=should(options, 'keepOnlyPositiveResiduals'),
                             prior_thresh=prior)
         diffs[s0:s0 + bs] = d[..., 0]
         l1[s0:s0 + bs] = e.cpu().numpy()
     if var is not None:
         model.last_epistemic_variance = var
+    if collector is not None:
+        collector['reconstructions'] = torch.cat(collector.pop('_recs'), dim=0) if S else diffs.clone()
+        collector['residual'] = diffs                      # median3d below returns a new tensor
     if should(options, 'medianFiltering'):
         diffs = eng.median3d(diffs, 5)
     return (diffs if device_out else diffs.cpu().numpy().astype(np.float64)), l1
@@ -268,10 +278,11 @@ def _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, opti
     ev['PrecisionCC'] = ev['TPCC'] / (ev['TPCC'] + ev['FPCC']) if ev['TPCC'] + ev['FPCC'] > 0 else 0.0
 
 
-def _score_diffs(model, diffs, labels, options, variances=None):
+def _score_diffs(model, diffs, labels, options, variances=None, keep=None):
     """The metric tail of utils/Evaluation.py:416-500 on per-patient residual volumes (device tensors [S,H,W]) and label maps: the
     voxel-wise scalars and, from _lesionwise_keys, TPCC / FPCC / FNCC / TPRCC / PrecisionCC, TP / FP / TN / FN / TPR / FPR / VD and the
-    per-patient means / standard deviations."""
+    per-patient means / standard deviations.  keep: None, or a dict that receives 'pred_dev', the final filtered prediction [P*S,H,W] on the
+    device (the overlay images of evaluate())."""
     d_all = torch.cat([d.reshape(-1) for d in diffs])
     l_all = np.concatenate([np.asarray(l).flatten() for l in labels])
     sc = model.engine.scores(d_all, l_all)
@@ -286,6 +297,8 @@ def _score_diffs(model, diffs, labels, options, variances=None):
     # filter), then the overall and per-patient Dice / precision / recall
     stacked = torch.cat(diffs, dim=0)
     pred_dev = model.engine.cc_filter((stacked > float(thr)).to(torch.float32), 7)
+    if keep is not None:
+        keep['pred_dev'] = pred_dev
     pred = pred_dev.cpu().numpy() > 0
     gts = [np.asarray(l).reshape(d.shape).astype(bool) for d, l in zip(diffs, labels)]
     ev['DiceScore'] = Metrics.dice(pred, np.concatenate(gts, axis=0))
@@ -427,11 +440,76 @@ def export_patient_volume(datasetObj, patient, nii_filename, subvolume, idx, sam
     return files
 
 
+def _render_ops(engine):
+    """(gray, heatmap, overlay, download): the device render ops of an engine that has them (engine._EvalOps.render_*), else the host statement
+    utils/render.py on downloaded arrays (the host stand-in engines of the CPU tests).  The images are the same either way."""
+    from . import render
+    if all(hasattr(engine, k) for k in ('render_gray', 'render_heatmap', 'render_overlay')):
+        return engine.render_gray, engine.render_heatmap, engine.render_overlay, lambda parts: torch.cat(list(parts), dim=0).cpu().numpy()
+
+    def host(a):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        return a[..., 0] if a.ndim == 4 else a
+    return (lambda a: render.minmax_u8(host(a)), lambda a: render.heatmap_rgba(host(a)), lambda x, p, g: render.overlay_rgb(host(x), host(p), host(g)),
+            lambda parts: np.concatenate(list(parts), axis=0))
+
+
+def export_patient_samples(engine, p, idx, x, seg, collected, diffs, sampleDir):
+    """options['exportSamples'] (utils/Evaluation.py:302-305, 316-321): for patient position p of the walk and every collected slice index s
+    of `idx` write {p}_{s}.png (input), {p}_{s}_rec.png (reconstruction), {p}_{s}_gt.png (label map), {p}_{s}_diff.png (residual before the
+    median), {p}_{s}_diff_filtered.png (after it) -- all normalize_and_squeeze -- and {p}_{s}_heatmap.png (squashed jet heat map of the filtered
+    residual with its colour bar).  Every kind is one render call over the patient's slices; the five grey stacks come back in one download,
+    the heat maps in a second.  The reference's `s - sliceStart` loop (:316) is clipped to the collected indices.
+    _rec_variance_combined.png, _logvar.png and the PDF / CSV histograms are out of scope.  Returns the files written."""
+    import os
+    from .png import write_png
+    gray, heatmap, _, download = _render_ops(engine)
+    kinds = ('', '_rec', '_gt', '_diff', '_diff_filtered')
+    stacks = (np.asarray(x, np.float32), collected['reconstructions'], np.asarray(seg).astype(np.float32), collected['residual'], diffs)
+    S = len(idx)
+    grey = download(gray(a) for a in stacks)                                # [5 S,H,W]
+    heat = download([heatmap(diffs)])                                       # [S,H,W,4]
+    files = []
+    for k, s in enumerate(idx):
+        for j, kind in enumerate(kinds):
+            files.append(os.path.join(sampleDir, '{}_{}{}.png'.format(p, s, kind)))
+            write_png(files[-1], grey[j * S + k])
+        files.append(os.path.join(sampleDir, '{}_{}_heatmap.png'.format(p, s)))
+        write_png(files[-1], heat[k])
+    return files
+
+
+def export_overlays(engine, x, pred_dev, labelmaps, positions, indices, sampleDir):
+    """options['exportSamples'] (utils/Evaluation.py:501-507): {p}_{s}_vis.png, the green / orange / red TP / FP / FN overlay of the final
+    filtered prediction on the input, for every patient position p of `positions` and slice index s of that patient's list in `indices` --
+    not the reference's idx % (sliceEnd - sliceStart) arithmetic, which breaks for a volume shorter than sliceEnd.  One render call and one
+    download for all patients.  The bytes are utils/render.py's overlay_rgb (a stated deviation from the reference's all-black
+    cv2.normalize(tmp, None, 0, 255))."""
+    import os
+    from .png import write_png
+    if not len(x):
+        return []
+    _, _, overlay, download = _render_ops(engine)
+    vis = download([overlay(np.asarray(x, np.float32), pred_dev, np.asarray(labelmaps) != 0)])
+    files, k = [], 0
+    for p, idx in zip(positions, indices):
+        for s in idx:
+            files.append(os.path.join(sampleDir, '{}_{}_vis.png'.format(p, s)))
+            write_png(files[-1], vis[k])
+            k += 1
+    assert k == len(vis), 'slice index lists and the stacked volume disagree'
+    return files
+
+
 def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
     """utils/Evaluation.py:183-365.  Walks the split's patients through the dataset duck-type, reconstructs every patient's slice stack in
     batched device calls and returns (eval_dict, patients): eval_dict['diffs'] [P*S,H,W] post-processed residuals (device tensor under
-    '_diffs_device' as well), 'labelmaps', 'x', 'l1reconstructionErrors' and their mean / variance.  The per-slice PNG dumps are not
-    written (sampleDir is created like the reference does).  options['resampleOnDevice']: the slice zoom (and the exportVolumes de-zoom)
+    '_diffs_device' as well), 'labelmaps', 'x', 'l1reconstructionErrors' and their mean / variance, and next to '_diffs_device' every used patient's
+    position in the walk and slice index list ('_patient_positions', '_slice_indices').  sampleDir is created like the reference does; the
+    per-slice PNG images (:302-321) are written when options['exportSamples'] is set (export_patient_samples: read like resampleOnDevice,
+    get_options does not set it, default off; _rec_variance_combined.png, _logvar.png and the PDF / CSV histograms stay out of scope).  Under
+    a process group with more than one rank a patient's owner writes that patient's files (not tested with more than one rank).
+    options['resampleOnDevice']: the slice zoom (and the exportVolumes de-zoom)
     run on the device spline op instead of scipy; options['exportVolumes']: export_patient_volume per patient."""
     import os
     os.makedirs(sampleDir, exist_ok=True)
@@ -441,7 +519,7 @@ def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
     diffs_dev = []
     variances = []               # numMonteCarloSamples > 1: every patient's epistemic-variance volume (utils/Evaluation.py:238-266,404-408)
     mc = int(options.get('numMonteCarloSamples') or 0) > 1
-    used = []
+    used, positions, indices = [], [], []
     zoom_engine = modelObj.engine if should(options, 'resampleOnDevice') else None      # opt-in: the default stays the host scipy path
     if zoom_engine is not None and not hasattr(zoom_engine, 'zoom'):
         raise RuntimeError("options['resampleOnDevice'] needs an engine with the device zoom op")
@@ -457,12 +535,16 @@ def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
                 continue
             x, seg, skull, prior_q, idx = got
             t0 = time.time()
-            d, l1 = evaluate_volume(modelObj, x, skull, options, eps, device_out=True, prior=prior_q)
-            rec = {'x': x, 'seg': seg, 'l1': list(l1), 'time': (time.time() - t0) / max(len(x), 1),
+            collected = {} if should(options, 'exportSamples') else None
+            d, l1 = evaluate_volume(modelObj, x, skull, options, eps, device_out=True, prior=prior_q, collector=collected)
+            rec = {'x': x, 'seg': seg, 'idx': list(idx), 'l1': list(l1), 'time': (time.time() - t0) / max(len(x), 1),
                    'var': modelObj.last_epistemic_variance.cpu().numpy() if mc else None}
             if should(options, 'exportVolumes') and _dp_rank_world()[0] == 0:
                 # one() runs on the patient's owner (_sharded_map): rank 0 writes the files of the patients of its own shard, the other ranks write none
                 export_patient_volume(datasetObj, patient, nii_filename, d, idx, sampleDir, options, engine=zoom_engine)
+            if collected is not None:
+                # one() runs on the patient's owner: that rank writes the patient's per-slice images
+                export_patient_samples(modelObj.engine, p, idx, x, seg, collected, d, sampleDir)
             return d, rec
         return None
     # patients are sharded over the ranks of an initialised process group (module docstring); every rank ends up with the full, ordered list
@@ -475,8 +557,10 @@ def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
             variances.append(rec['var'])
         ev['x'].append(rec['x']); ev['labelmaps'].append(rec['seg']); ev['l1reconstructionErrors'] += rec['l1']
         used.append(patients[p])
+        positions.append(p); indices.append(rec['idx'])
     print("Done.")
     ev['_diffs_device'] = diffs_dev
+    ev['_patient_positions'], ev['_slice_indices'] = positions, indices
     ev['_variances'] = variances
     ev['diffs'] = np.concatenate([d.cpu().numpy().astype(np.float64) for d in diffs_dev], axis=0) if diffs_dev else np.zeros((0,))
     ev['x'] = np.concatenate(ev['x'], axis=0) if ev['x'] else np.zeros((0,))
@@ -501,7 +585,9 @@ def _eval_dir(model, options, epoch, description):
 def evaluate(datasetPC, gan, options, epoch='last', description=None, eps=None):
     """utils/Evaluation.py:372-526 with the reference's signature: evaluates the TEST patients of `datasetPC`, writes evalPC.npy / evalPC.txt
     (+ rocPC.npy / prcPC.npy when options['exportROC'] / ['exportPRC']) under <SAMPLEDIR>/<network>/<model_dir>/eval-<epoch>-<timestamp>[-
-    <description>]/ and -- unlike the reference, which returns None -- hands the scalar dictionary back."""
+    <description>]/ and -- unlike the reference, which returns None -- hands the scalar dictionary back.  options['exportSamples']: _evaluate
+    fills samples_test_PC/ with the per-slice images and rank 0 adds {p}_{s}_vis.png (export_overlays, :501-507).  The PDF / CSV histograms,
+    _rec_variance_combined.png and _logvar.png are not written."""
     import os
     t_all = time.time()
     rank0 = _dp_rank_world()[0] == 0          # every rank scores the same gathered patient list; rank 0 alone writes the files
@@ -510,8 +596,12 @@ def evaluate(datasetPC, gan, options, epoch='last', description=None, eps=None):
     eval_pc, patients_pc = _evaluate(datasetPC, gan, sample_dir, options, split="TEST", eps=eps)
     diffs = eval_pc.pop('_diffs_device')
     variances = eval_pc.pop('_variances')
+    positions, indices = eval_pc.pop('_patient_positions'), eval_pc.pop('_slice_indices')
     labels = [eval_pc['labelmaps'][sum(d.shape[0] for d in diffs[:k]):sum(d.shape[0] for d in diffs[:k + 1])] for k in range(len(diffs))]
-    ev = _score_diffs(gan, diffs, labels, options, variances)
+    kept = {} if should(options, 'exportSamples') else None
+    ev = _score_diffs(gan, diffs, labels, options, variances, keep=kept)
+    if kept is not None and rank0:
+        export_overlays(gan.engine, eval_pc['x'], kept['pred_dev'], eval_pc['labelmaps'], positions, indices, sample_dir)
     for k in ('l1reconstructionErrorMean', 'l1reconstructionErrorVariance', 'l2reconstructionErrorMean', 'l2reconstructionErrorVariance',
               'reconstructionTimes'):
         ev[k] = eval_pc[k]
