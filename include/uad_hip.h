@@ -478,14 +478,44 @@ int uad_render_overlay(const float* x, const float* pred, const uint8_t* gt, int
  * uad_histogram_edges: counts[i] (int64 [bins], device) = the number of values with edges[i] <= v < edges[i + 1], the last bin closed
  *   (v <= edges[bins]); values outside [edges[0], edges[bins]] and NaNs are dropped.  edges: bins + 1 fp32 on the device, non-decreasing, bins <=
  *   UAD_HISTOGRAM_MAX_BINS.  With the table np.histogram_bin_edges gives this is np.histogram (utils/Evaluation.py:404-408: 50 bins).
- * uad_clamp_scale: out[i] = (v < lo ? lo : v > hi ? hi : v) * scale, the clamp-and-scale tail of utils/NII.py:57-66; out may alias in. */
+ * uad_clamp_scale: out[i] = (v < lo ? lo : v > hi ? hi : v) * scale, the clamp-and-scale tail of utils/NII.py:57-66; out may alias in.
+ * uad_select_quantiles_masked: uad_select_quantiles of ONE segment of n values restricted to the values with labels[i] == class_id (labels:
+ *   u8 [n], device) and lo <= v <= hi (fp32 bounds from the host, formed so that the fp32 test equals the caller's fp64 one) -- the
+ *   `data[labels == classes[0]]` of utils/utils.py:49 cut to the histogram range as np.histogram's bins='auto' cuts it (utils/Evaluation.py:
+ *   399-402).  q = {0, 0.25, 0.75, 1} gives what numpy's 'auto' width needs: m, min, max and the brackets of both quartiles.  Same kernels
+ *   (a template parameter), same contract: m, the bracketing order statistics per fraction, integer atomics only, bit-reproducible, no host
+ *   synchronisation, workspace of uad_select_workspace(1) bytes.  n <= 2^31 - 1.
+ * uad_histogram_by_class (csrc/uad_hist.hip): plot_histogram_with_labels (utils/utils.py:44-71, called at utils/Evaluation.py:400-402 and
+ *   :409-411) in one pass over `in` (fp32 [n], device) and `labels` (u8 [n] class ids 0 .. n_classes - 1, n_classes <=
+ *   UAD_HISTOGRAM_MAX_CLASSES; ids at or above n_classes are dropped):
+ *   counts[c][i] (int64 [n_classes, bins], device) on ONE shared edge table with the bin rule of uad_histogram_edges (last bin closed, NaN
+ *   and out-of-table values dropped; a non-monotone table is the caller's error), bins <= UAD_HISTOGRAM_MAX_BINS a call -- a longer table is
+ *   counted in chunks, one call each, every chunk but the last with its last edge lowered by one fp32 ulp; bins == 0: no histogram (edges
+ *   and counts may be NULL);
+ *   class_count[c] (int64 [n_classes]) and sums[c] (fp64 [n_classes]) over ALL values of class c, in the table or not: sum of v with centre
+ *   == NULL, else sum of (v - centre[c])^2 (centre: fp64 [n_classes], device).  Two calls give the two-pass np.mean / np.var of :53: the
+ *   first without a table, the second with the means as centres.  class_count == sums == NULL: counts only (no workspace needed).
+ *   Counters are privatised in LDS per workgroup and added to the global ones with integer atomics.  The fp64 sums use NO floating-point
+ *   atomic: a thread adds 32 values, the workgroup adds its 256 runs as a tree in a fixed order, one partial per tile of UAD_SELECT_TILE
+ *   values goes to the workspace, one workgroup adds the partials (256 strided runs, the same tree).  Bit-identical from run to run and
+ *   independent of the grid.  The longest chain of dependent additions is 32 + 8 + ceil(tiles / 256) + 8 <= UAD_HISTOGRAM_SUM_CHAIN for every
+ *   accepted n, so a sum errs by at most UAD_HISTOGRAM_SUM_CHAIN * 2^-53 * sum |terms|.
+ *   workspace: device memory of at least uad_histogram_by_class_workspace(n) bytes (64 per tile), 16-byte aligned, owned by the caller, any
+ *   contents.  n == 0: UAD_OK, nothing launched, outputs zeroed.  UAD_ERR_INVALID: a NULL pointer that is needed, a negative size, n_classes
+ *   outside 1 .. 4, bins above the limit, a short or misaligned workspace.  UAD_ERR_UNSUPPORTED: n > 2^31 - 1. */
 enum { UAD_SELECT_ALL = 0, UAD_SELECT_NONNEG = 1 };
 enum { UAD_SELECT_MAX_Q = 4, UAD_SELECT_TILE = 8192, UAD_HISTOGRAM_MAX_BINS = 1024 };
+enum { UAD_HISTOGRAM_MAX_CLASSES = 4, UAD_HISTOGRAM_SUM_CHAIN = 1073 };
 size_t uad_select_workspace(int n_seg);
 int uad_select_quantiles(const float* in, int n_seg, long long n_per_seg, const double* q, int k, unsigned f32_index_mask, int filter,
                          long long* m_out, float* bracket_out, void* workspace, size_t workspace_bytes, void* stream);
 int uad_histogram_edges(const float* in, long long n, const float* edges, int bins, long long* counts, void* stream);
 int uad_clamp_scale(const float* in, long long n, float lo, float hi, float scale, float* out, void* stream);
+int uad_select_quantiles_masked(const float* in, const uint8_t* labels, long long n, int class_id, float lo, float hi, const double* q, int k,
+                                unsigned f32_index_mask, long long* m_out, float* bracket_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t uad_histogram_by_class_workspace(long long n);
+int uad_histogram_by_class(const float* in, const uint8_t* labels, long long n, int n_classes, const float* edges, int bins, const double* centre,
+                           long long* counts, long long* class_count, double* sums, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- f-AnoGAN (unified graph) ------------------------------------------------------------------------------
  * Replaces models/fanogan.py:11-84 (encoder + generator + critic graph) and the three optimisation phases of

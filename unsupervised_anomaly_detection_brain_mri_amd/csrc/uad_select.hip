@@ -10,6 +10,9 @@
 //                          virtual index (m - 1) * q, in the float type numpy forms it in (one multiply, no contraction).
 //                          No key array, no scatter, no second copy: 4 x 4 B x n of HBM reads per call, and integer atomics only, so the
 //                          result is bit-reproducible and a segment's result does not depend on its neighbours.
+//                          uad_select_quantiles_masked (utils/utils.py:44-50 under utils/Evaluation.py:399-402: the values of ONE class inside
+//                          a value range, numpy's `a[keep]` of bins='auto') is the MASKED instantiation of the same kernel: the filter is
+//                          labels[i] == class_id && lo <= v <= hi, everything after the filter is shared.
 //   2. hist_edges_kernel   histogram over a caller-given edge table (binary search in LDS), per-wave LDS histograms, 64-bit integer atomics.
 //   3. clamp_scale_kernel  out = clamp(v, lo, hi) * s as numpy's `v[v < lo] = lo; v[v > hi] = hi; v * s` writes it.
 // Bandwidth- and latency-shaped work: no matrix cores, vector stores only.
@@ -47,6 +50,13 @@ struct SelState {
     unsigned pad[5];
 };
 static_assert(sizeof(SelState) % 16 == 0, "the counters behind the states stay 16-byte aligned");
+
+// the MASKED instantiation's filter (unused by the other one)
+struct SelMask {
+    const uint8_t* labels;
+    float lo, hi;
+    int class_id;
+};
 
 struct SelQ {
     double q[UAD_SELECT_MAX_Q];
@@ -100,9 +110,10 @@ __device__ __forceinline__ void bracket_ranks(unsigned long long m, double q, bo
     *hi = (unsigned long long)n;
 }
 
+template <bool MASKED>
 __global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(const float* __restrict__ in, unsigned long long n_per_seg, int pass, int filter,
                                                                   SelQ qs, SelState* __restrict__ states, unsigned* __restrict__ counts,
-                                                                  long long* __restrict__ out_m, float* __restrict__ out_vals) {
+                                                                  long long* __restrict__ out_m, float* __restrict__ out_vals, SelMask mk) {
     __shared__ unsigned hist[SEL_WAVES][SEL_TARGETS][256];       // 32 KB
     __shared__ unsigned long long scan_buf[SEL_THREADS];
     __shared__ unsigned long long s_rank[SEL_TARGETS];
@@ -149,6 +160,12 @@ __global__ void __launch_bounds__(SEL_THREADS) select_pass_kernel(const float* _
                 ok[e] = j0 + e >= off && j0 + e < end;
                 v[e] = ok[e] ? aligned[j0 + e] : 0.f;
             }
+        }
+        if constexpr (MASKED) {
+            // one segment: element j of the aligned index space is value j - off, and so is its class id (read only where the value was)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                ok[e] = ok[e] && mk.labels[j0 + e - off] == (uint8_t)mk.class_id && v[e] >= mk.lo && v[e] <= mk.hi;
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -367,8 +384,39 @@ int uad_select_quantiles(const float* in, int n_seg, long long n_per_seg, const 
     SEL_TRY(hipMemsetAsync(workspace, 0, need, st));
     const dim3 grid((unsigned)select_tiles((unsigned long long)n_per_seg), (unsigned)n_seg);
     for (int pass = 0; pass < 4; ++pass) {
-        hipLaunchKernelGGL(select_pass_kernel, grid, dim3(SEL_THREADS), 0, st, in, (unsigned long long)n_per_seg, pass, filter, qs, states, counts,
-                           m_out, bracket_out);
+        hipLaunchKernelGGL(select_pass_kernel<false>, grid, dim3(SEL_THREADS), 0, st, in, (unsigned long long)n_per_seg, pass, filter, qs, states, counts,
+                           m_out, bracket_out, SelMask{nullptr, 0.f, 0.f, 0});
+        SEL_TRY(hipGetLastError());
+    }
+    return UAD_OK;
+}
+
+int uad_select_quantiles_masked(const float* in, const uint8_t* labels, long long n, int class_id, float lo, float hi, const double* q, int k,
+                                unsigned f32_index_mask, long long* m_out, float* bracket_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!in || !labels || !q || !m_out || !bracket_out || !workspace) return fail(UAD_ERR_INVALID, "select_quantiles_masked: bad arguments");
+    if (n <= 0 || n > 0x7fffffffLL) return fail(UAD_ERR_INVALID, "select_quantiles_masked: 1 .. 2^31 - 1 values, got %lld", n);
+    if (k <= 0 || k > UAD_SELECT_MAX_Q) return fail(UAD_ERR_INVALID, "select_quantiles_masked: 1 .. %d quantiles, got %d", UAD_SELECT_MAX_Q, k);
+    if (class_id < 0 || class_id > 255) return fail(UAD_ERR_INVALID, "select_quantiles_masked: class ids are 0 .. 255, got %d", class_id);
+    if (!(lo <= hi)) return fail(UAD_ERR_INVALID, "select_quantiles_masked: the range [%g, %g] is empty or not a number", (double)lo, (double)hi);
+    if (((uintptr_t)in & 3) != 0) return fail(UAD_ERR_INVALID, "select_quantiles_masked: input must be 4-byte aligned");
+    SelQ qs;
+    qs.k = k;
+    qs.f32_mask = f32_index_mask;
+    for (int j = 0; j < UAD_SELECT_MAX_Q; ++j) {
+        qs.q[j] = j < k ? q[j] : 0.0;
+        if (!(qs.q[j] >= 0.0 && qs.q[j] <= 1.0)) return fail(UAD_ERR_INVALID, "select_quantiles_masked: q[%d] = %g is outside [0, 1]", j, qs.q[j]);
+    }
+    const size_t need = uad_select_workspace(1);
+    if (workspace_bytes < need) return fail(UAD_ERR_INVALID, "select_quantiles_masked: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (((uintptr_t)workspace & 15) != 0) return fail(UAD_ERR_INVALID, "select_quantiles_masked: workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    SelState* states = (SelState*)workspace;
+    unsigned* counts = (unsigned*)(states + 1);
+    SEL_TRY(hipMemsetAsync(workspace, 0, need, st));
+    const dim3 grid((unsigned)select_tiles((unsigned long long)n), 1u);
+    for (int pass = 0; pass < 4; ++pass) {
+        hipLaunchKernelGGL(select_pass_kernel<true>, grid, dim3(SEL_THREADS), 0, st, in, (unsigned long long)n, pass, (int)UAD_SELECT_ALL, qs, states, counts,
+                           m_out, bracket_out, SelMask{labels, lo, hi, class_id});
         SEL_TRY(hipGetLastError());
     }
     return UAD_OK;

@@ -502,6 +502,139 @@ class _EvalOps(OrderStatOps):
                                             float(scale), _ptr(out), self._stream()))
         return out
 
+    # ---------------------------------------------------------------- per-class histograms (csrc/uad_select.hip, csrc/uad_hist.hip)
+    def _class_ids(self, ids, n):
+        """-> contiguous uint8 device tensor [n] of class ids (a numpy array or a tensor of any integer type)."""
+        t = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ids))
+        t = t.reshape(-1).to(self.device).to(torch.uint8).contiguous()
+        if t.numel() != n:
+            raise ValueError(f'{t.numel()} class ids for {n} values')
+        return t
+
+    def select_quantiles_masked(self, values, ids, class_id, lo32, hi32, fractions, f32_index, workspace=None):
+        """uad_select_quantiles_masked: select_quantiles of the values v with ids == class_id and lo32 <= v <= hi32 (float32 bounds).
+        -> (m int, lo [k] float32, hi [k] float32) on the host; NaN brackets when m == 0."""
+        t = self._f32_exact(values).reshape(-1)
+        lab = self._class_ids(ids, t.numel())
+        k = len(fractions)
+        if t.numel() == 0:
+            raise ValueError('no values to select from')
+        if not 1 <= k <= _lib.SELECT_MAX_Q or len(f32_index) != k:
+            raise ValueError(f'1 .. {_lib.SELECT_MAX_Q} fractions with one index type each, got {k} / {len(f32_index)}')
+        ws = workspace if workspace is not None else self.select_workspace(1)
+        m = torch.empty(1, device=self.device, dtype=torch.int64)
+        br = torch.empty(2 * k, device=self.device, dtype=torch.float32)
+        q = (C.c_double * k)(*[float(v) for v in fractions])
+        mask = sum(1 << j for j, f in enumerate(f32_index) if f)
+        _lib.check(self.lib.uad_select_quantiles_masked(_ptr(t), _ptr(lab), t.numel(), int(class_id), float(lo32), float(hi32), q, k, mask, _ptr(m), _ptr(br),
+                                                        _ptr(ws), ws.numel() * ws.element_size(), self._stream()))
+        br = br.cpu().numpy()
+        return int(m.cpu().numpy()[0]), br[0::2], br[1::2]
+
+    def histogram_workspace(self, n):
+        """A workspace tensor for histogram_by_class calls over up to n values (any contents)."""
+        nbytes = int(self.lib.uad_histogram_by_class_workspace(int(n)))
+        return torch.empty(max(nbytes // 8, 2), device=self.device, dtype=torch.int64)
+
+    def histogram_by_class(self, values, ids, n_classes, edges32=None, centre=None, moments=True, workspace=None):
+        """uad_histogram_by_class, nothing downloaded: (counts int64 [n_classes, bins] or None without edges32, class_count int64 [n_classes],
+        sums float64 [n_classes]) as DEVICE tensors (the last two None with moments=False).  sums = sum of v per class, or with centre (float64
+        [n_classes], device tensor or array) the sum of (v - centre[c])^2, over all values of the class.  A table of more than
+        HISTOGRAM_MAX_BINS bins is counted in chunks of that many, one launch each: a chunk that is not the last gets its last edge lowered by
+        one float32 ulp, which closes it exactly where the next one opens."""
+        t = self._f32_exact(values).reshape(-1)
+        n, k = t.numel(), int(n_classes)
+        lab = self._class_ids(ids, n)
+        bins = 0 if edges32 is None else len(edges32) - 1
+        if bins == 0 and not moments:
+            raise ValueError('neither a histogram nor moments asked for')
+        cen = None
+        if centre is not None:
+            cen = (centre if isinstance(centre, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centre, np.float64))).to(self.device, torch.float64).contiguous()
+            if cen.numel() != k:
+                raise ValueError(f'{cen.numel()} centres for {k} classes')
+        cnt = torch.empty(k, device=self.device, dtype=torch.int64) if moments else None
+        sums = torch.empty(k, device=self.device, dtype=torch.float64) if moments else None
+        ws = None
+        if moments:
+            ws = workspace if workspace is not None else self.histogram_workspace(n)
+        ws_bytes = 0 if ws is None else ws.numel() * ws.element_size()
+        if bins == 0:
+            _lib.check(self.lib.uad_histogram_by_class(_ptr(t), _ptr(lab), n, k, None, 0, _ptr(cen), None, _ptr(cnt), _ptr(sums), _ptr(ws), ws_bytes, self._stream()))
+            return None, cnt, sums
+        e = np.ascontiguousarray(edges32, np.float32)
+        counts = torch.empty((k, bins), device=self.device, dtype=torch.int64)
+        step = _lib.HISTOGRAM_MAX_BINS
+        for c0 in range(0, bins, step):
+            nb = min(step, bins - c0)
+            sub = e[c0:c0 + nb + 1].copy()
+            if c0 + nb < bins:
+                sub[-1] = np.nextafter(sub[-1], np.float32(-np.inf))
+            ed = torch.from_numpy(sub).to(self.device)
+            part = counts if nb == bins else torch.empty((k, nb), device=self.device, dtype=torch.int64)
+            first = c0 == 0 and moments
+            _lib.check(self.lib.uad_histogram_by_class(_ptr(t), _ptr(lab), n, k, _ptr(ed), nb, _ptr(cen), _ptr(part), _ptr(cnt) if first else None,
+                                                       _ptr(sums) if first else None, _ptr(ws) if first else None, ws_bytes if first else 0, self._stream()))
+            if part is not counts:
+                counts[:, c0:c0 + nb] = part
+        return counts, cnt, sums
+
+    def labelled_histogram(self, values, labels, bins, range, as_dtype=None):
+        """utils.histograms.labelled_histograms(values, labels, bins, range) -- the reference's plot_histogram_with_labels (utils/utils.py:44-71)
+        -- on the device: [{'class', 'n', 'bins', 'mean', 'var'}] per class of np.unique(labels).  values: a device fp32 tensor, or a float32 /
+        float64 array whose values are float32 numbers (ValueError otherwise); labels: a numpy array or a tensor of values' shape (the unique
+        classes and the uint8 class ids are formed on the host and uploaded once).  bins: 'auto', an integer or an edge array.  as_dtype: the
+        numpy dtype the statement would see (default: that of `values`) -- it decides the type of the edges and of the range test, exactly
+        as in numpy; float64 for fp32 residuals whose host copy is float64.  'auto' takes one masked select (class 0 inside the range) and
+        the host half utils.histograms.auto_bin_count; then two histogram launches (sums, then counts and centred squares) and ONE download.
+        Counts and edges are numpy's exactly; mean and var are two-pass fp64 sums in a fixed order (utils.histograms.TooManyBins above
+        MAX_DEVICE_BINS bins: the caller takes the host statement)."""
+        import operator
+        from .utils import histograms as H
+        from .utils.order_stats import edges_to_float32, value_dtype
+        dtype = np.dtype(as_dtype) if as_dtype is not None else value_dtype(values)
+        if dtype not in (np.float32, np.float64):
+            raise TypeError(f'histograms take float32 or float64 values, got {dtype}')
+        t = self._f32_exact(values).reshape(-1)
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        if lab.size != t.numel():
+            raise ValueError(f'{lab.size} labels for {t.numel()} values')
+        classes, ids = H.class_ids(lab)
+        k = classes.size
+        if k == 0:
+            return []
+        ids = self._class_ids(ids, t.numel())
+        if isinstance(bins, str):
+            if bins != 'auto':
+                raise ValueError(f"bins: 'auto', an integer or an edge array, got {bins!r}")
+            first, last = H.outer_edges(range)
+            lo32, hi32 = H.range_to_float32(first, last, dtype)
+            m, lo, hi = self.select_quantiles_masked(t, ids, 0, lo32, hi32, H.AUTO_Q, [False] * len(H.AUTO_Q))
+            n_bins = H.auto_bin_count(m, lo[0], hi[3], (lo[1], hi[1]), (lo[2], hi[2]), range, dtype)
+            if n_bins > H.MAX_DEVICE_BINS:
+                raise H.TooManyBins(n_bins)
+            edges = H.equal_bin_edges(n_bins, range, dtype)
+        elif np.ndim(bins) == 0:
+            if operator.index(bins) > H.MAX_DEVICE_BINS:
+                raise H.TooManyBins(operator.index(bins))
+            edges = H.equal_bin_edges(operator.index(bins), range, dtype)
+        else:
+            edges = np.asarray(bins)
+            if edges.ndim != 1 or edges.size < 2 or np.any(edges[:-1] > edges[1:]):
+                raise ValueError('`bins` must be 1d and increase monotonically, when an array')
+            if edges.size - 1 > H.MAX_DEVICE_BINS:
+                raise H.TooManyBins(edges.size - 1)
+        ws = self.histogram_workspace(t.numel())
+        _, cnt, sums = self.histogram_by_class(t, ids, k, workspace=ws)
+        mean = sums / cnt.to(torch.float64)                           # k fp64 divisions, on the device: no download between the launches
+        counts, _, sq = self.histogram_by_class(t, ids, k, edges32=edges_to_float32(edges), centre=mean, workspace=ws)
+        var = sq / cnt.to(torch.float64)
+        flat = torch.cat([counts.reshape(-1), mean.view(torch.int64), var.view(torch.int64)]).cpu().numpy()
+        nb = edges.size - 1
+        n = flat[:k * nb].reshape(k, nb).astype(np.float64)
+        mean, var = flat[k * nb:k * nb + k].view(np.float64), flat[k * nb + k:].view(np.float64)
+        return [{'class': c, 'n': n[i], 'bins': edges, 'mean': mean[i], 'var': var[i]} for i, c in enumerate(classes)]
+
     def scores(self, predictions, labels):
         """One descending device sort of all voxel scores -> Scores object (AUROC, AUPRC, dice at thresholds)."""
         return Scores(self, predictions, labels)

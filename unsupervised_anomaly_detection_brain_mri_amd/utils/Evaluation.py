@@ -3,7 +3,8 @@ description)` (:372-526), `_evaluate(datasetObj, modelObj, sampleDir, options, s
 `determine_threshold_on_labeled_patients(dataset_pc, model, options, epoch, description)` (:529-570) on the dataset duck-type
 (`patients`, `get_patient_idx`, `load_volume_and_groundtruth`, `options.{sliceStart, sliceEnd, axis, sliceResolution}`), over the
 array-level core `evaluate_arrays` / `evaluate_volume` (options['exportVolumes'] writes the NIfTI volumes, options['exportSamples'] the per-slice
-PNG images of samples_test_PC/, rendered to 8 bits on the device: export_patient_samples / export_overlays; the PDF / CSV histograms are dropped).  Everything between the reconstruction and the scalar metrics stays on the device:
+PNG images of samples_test_PC/, rendered to 8 bits on the device: export_patient_samples / export_overlays; options['exportHistograms'] the per-class
+histograms of the residuals and of the epistemic variances as .npy / .csv files: export_histograms -- the PDF plots are not drawn).  Everything between the reconstruction and the scalar metrics stays on the device:
 slices of a volume are reconstructed in ONE batched call (the reference runs one sess.run per slice, :246-250), the brain
 masks are eroded (uad_erode_cross), residual map + mask + hyper-intensity prior come from uad_residual, the 5x5x5 median is
 uad_median3d, and AUROC / AUPRC / the Dice threshold sweep read one device sort of all voxels (uad_scores_*).
@@ -282,7 +283,8 @@ def _score_diffs(model, diffs, labels, options, variances=None, keep=None):
     """The metric tail of utils/Evaluation.py:416-500 on per-patient residual volumes (device tensors [S,H,W]) and label maps: the
     voxel-wise scalars and, from _lesionwise_keys, TPCC / FPCC / FNCC / TPRCC / PrecisionCC, TP / FP / TN / FN / TPR / FPR / VD and the
     per-patient means / standard deviations.  keep: None, or a dict that receives 'pred_dev', the final filtered prediction [P*S,H,W] on the
-    device (the overlay images of evaluate())."""
+    device (the overlay images of evaluate()), and with Monte-Carlo variances 'variance_p998', their 99.8th percentile (the range of the
+    variance histograms of evaluate())."""
     d_all = torch.cat([d.reshape(-1) for d in diffs])
     l_all = np.concatenate([np.asarray(l).flatten() for l in labels])
     sc = model.engine.scores(d_all, l_all)
@@ -326,6 +328,8 @@ def _score_diffs(model, diffs, labels, options, variances=None, keep=None):
             pos = ev['epistemic_variance'][ev['epistemic_variance'] >= 0]
             hi = float(np.percentile(pos, 99.8))
             hist = lambda: np.histogram(ev['epistemic_variance'], bins=50, range=(1e-5, hi))[0]
+        if keep is not None:
+            keep['variance_p998'] = hi
         # (the reference's np.histogram raises when every variance is below 1e-5; an empty histogram is returned here instead)
         ev['uncertaintyHistogram'] = (hist() if hi > 1e-5 else np.zeros(50, np.int64)).tolist()
     return ev
@@ -501,6 +505,48 @@ def export_overlays(engine, x, pred_dev, labelmaps, positions, indices, sampleDi
     return files
 
 
+HISTOGRAM_RANGE = (0.01, 0.075)          # utils/Evaluation.py:376, the range of the residual histograms
+_told_host_histogram = False
+
+
+def _labelled_histograms(engine, values, host_values, labels, bins, range):
+    """utils/utils.py:44-53 for one call site: engine.labelled_histogram (one masked select for 'auto', two histogram launches, one small
+    download) on `values` -- a device fp32 tensor or a host array -- when the engine has it, else the host statement
+    utils/histograms.labelled_histograms on host_values (the host stand-in engines of the CPU tests); the statement also takes an edge
+    table of more than histograms.MAX_DEVICE_BINS bins and says so once on stderr."""
+    global _told_host_histogram
+    from . import histograms
+    fn = getattr(engine, 'labelled_histogram', None)
+    if fn is not None:
+        try:
+            return fn(values, labels, bins, range, as_dtype=host_values.dtype)
+        except histograms.TooManyBins as e:
+            if not _told_host_histogram:
+                import sys
+                print(f'exportHistograms: {e} bins are more than {histograms.MAX_DEVICE_BINS}; the histograms are computed on the host', file=sys.stderr)
+                _told_host_histogram = True
+    return histograms.labelled_histograms(host_values.reshape(-1), np.asarray(labels).reshape(-1), bins, range)
+
+
+def export_histograms(engine, diffs, host_diffs, labelmaps, variances, variance_p998, eval_dir):
+    """options['exportHistograms'] (utils/Evaluation.py:399-411): plot_histogram_with_labels of the residuals (bins 'auto', range 0.01 ..
+    0.075) -> testing_lesions_diffimages_histogram.{i}.npy / .pdf.{i}.csv per class i, and with Monte-Carlo sampling of the epistemic
+    variances (50 bins, 1e-5 .. their 99.8th percentile; skipped when that is not above 1e-5, as uncertaintyHistogram is) ->
+    testing_lesions_epistemic_variances_histogram.{i}.npy / .pdf.{i}.csv.  diffs: the per-patient device residual volumes; host_diffs:
+    their float64 host copy (what the reference histograms); labelmaps [P*S,H,W]; variances: the stacked host variance volume or None.
+    No PDF is drawn.  Returns the files written."""
+    from . import histograms
+    files = []
+    lab = np.asarray(labelmaps).reshape(-1)
+    res = _labelled_histograms(engine, torch.cat([d.reshape(-1) for d in diffs]), np.asarray(host_diffs), lab, 'auto', HISTOGRAM_RANGE)
+    files += histograms.write_labelled_histograms(res, eval_dir, 'testing_lesions_diffimages_histogram')
+    if variances is not None and variance_p998 is not None and variance_p998 > 1e-5:
+        var = np.asarray(variances)
+        res = _labelled_histograms(engine, var, var, lab, 50, (1e-5, variance_p998))
+        files += histograms.write_labelled_histograms(res, eval_dir, 'testing_lesions_epistemic_variances_histogram')
+    return files
+
+
 def _evaluate(datasetObj, modelObj, sampleDir, options, split="TEST", eps=None):
     """utils/Evaluation.py:183-365.  Walks the split's patients through the dataset duck-type, reconstructs every patient's slice stack in
     batched device calls and returns (eval_dict, patients): eval_dict['diffs'] [P*S,H,W] post-processed residuals (device tensor under
@@ -586,8 +632,11 @@ def evaluate(datasetPC, gan, options, epoch='last', description=None, eps=None):
     """utils/Evaluation.py:372-526 with the reference's signature: evaluates the TEST patients of `datasetPC`, writes evalPC.npy / evalPC.txt
     (+ rocPC.npy / prcPC.npy when options['exportROC'] / ['exportPRC']) under <SAMPLEDIR>/<network>/<model_dir>/eval-<epoch>-<timestamp>[-
     <description>]/ and -- unlike the reference, which returns None -- hands the scalar dictionary back.  options['exportSamples']: _evaluate
-    fills samples_test_PC/ with the per-slice images and rank 0 adds {p}_{s}_vis.png (export_overlays, :501-507).  The PDF / CSV histograms,
-    _rec_variance_combined.png and _logvar.png are not written."""
+    fills samples_test_PC/ with the per-slice images and rank 0 adds {p}_{s}_vis.png (export_overlays, :501-507).
+    options['exportHistograms'] (read from the dictionary like exportSamples; get_options does not set it, default off): rank 0 writes the
+    per-class histograms of the residuals -- with Monte-Carlo sampling also of the epistemic variances -- as .npy pickles and .csv tables
+    (export_histograms, :399-411); nothing is added to the saved dictionary.  The PDF plots of those histograms, the reference's
+    diffHistogram (computed there and dropped before saving), _rec_variance_combined.png and _logvar.png are not written."""
     import os
     t_all = time.time()
     rank0 = _dp_rank_world()[0] == 0          # every rank scores the same gathered patient list; rank 0 alone writes the files
@@ -598,9 +647,11 @@ def evaluate(datasetPC, gan, options, epoch='last', description=None, eps=None):
     variances = eval_pc.pop('_variances')
     positions, indices = eval_pc.pop('_patient_positions'), eval_pc.pop('_slice_indices')
     labels = [eval_pc['labelmaps'][sum(d.shape[0] for d in diffs[:k]):sum(d.shape[0] for d in diffs[:k + 1])] for k in range(len(diffs))]
-    kept = {} if should(options, 'exportSamples') else None
+    kept = {} if should(options, 'exportSamples') or should(options, 'exportHistograms') else None
     ev = _score_diffs(gan, diffs, labels, options, variances, keep=kept)
-    if kept is not None and rank0:
+    if should(options, 'exportHistograms') and rank0:
+        export_histograms(gan.engine, diffs, eval_pc['diffs'], eval_pc['labelmaps'], ev.get('epistemic_variance'), kept.get('variance_p998'), eval_dir)
+    if should(options, 'exportSamples') and rank0:
         export_overlays(gan.engine, eval_pc['x'], kept['pred_dev'], eval_pc['labelmaps'], positions, indices, sample_dir)
     for k in ('l1reconstructionErrorMean', 'l1reconstructionErrorVariance', 'l2reconstructionErrorMean', 'l2reconstructionErrorVariance',
               'reconstructionTimes'):
