@@ -238,7 +238,7 @@ int uad_get_math_mode(const uad_model_t* m);
  * sign(x_hat - x) / n per pixel; both report count 0 otherwise), "dec_in" = the decoder's pre-BN input, "G0" / "G1" = gradient
  * ping-pong buffers, "fused_final" = flag in *count. */
 int uad_debug_buffer(uad_model_t* m, const char* name, float** ptr, long long* count);
-/* tests: what the handle WOULD launch for one 5x5 block at batch n (1 .. max_batch) in its current math mode; nothing is launched and no state changes.
+/* tests: what the handle WOULD launch for one 5x5 block (or the dense bottleneck: side 2) at batch n (1 .. max_batch) in its current math mode; nothing is launched and no state changes.
  * side 0 = encoder block `layer` (>= 1; block 0 runs the one-channel first-layer kernels: only its 'W' is answered, kernel 3, with the slab floats it needs),
  * side 1 = decoder block `layer`; kind 'F' | 'D' | 'W' after
  * the launchers (encoder: F forward, D data gradient; decoder: D forward, F data gradient; W filter gradient).  out[12]:
@@ -248,7 +248,17 @@ int uad_debug_buffer(uad_model_t* m, const char* name, float** ptr, long long* c
  *          10 BN column-partial floats a data gradient writes (0 for a forward), 11 ... allocated per slot;
  *   W:     0 kernel (0 generic | 1 k5 s2 tile kernel | 2 k3 tap-list kernel | 3 first-layer kernel), 1 splits, 2 last split short, 3 32-channel cs blocks per workgroup (k5: 1 | 2),
  *          4 work units (8 x 8 output tiles; generic: 32-position K steps), 5 bf16x6 three-plane kernel (1 | 0 | -1), 6 -1, 7 units per split,
- *          8 filter-gradient slab floats needed, 9 ... allocated per slot, 10 0, 11 as above. */
+ *          8 filter-gradient slab floats needed, 9 ... allocated per slot, 10 0, 11 as above.
+ * side 2 = the dense bottleneck between encoder and decoder (AE / VAE / ceVAE handles; UAD_ERR_INVALID on the others), layer 0, kind 'B'.  out[12]:
+ *   B:     0 fused forward / backward, one kernel each (1 | 0: the chain of generic 1x1 / dense launches), 1 workgroups per sample (1 | 4: partial vectors exchanged
+ *          through global memory), 2 parameter gradients in one fused launch (1 | 0: four filter-gradient GEMMs + column sums | -1 when 0 is unfused: the GEMMs
+ *          are the only way), 3 k-groups the 1024 threads form over a workgroup's feature slice (1024 / slice width when the slice is narrower, else 1; the slice
+ *          is all of inter_res^2 * cmid features with one workgroup per sample; on an unfused handle 1 and 3 are what uad_bottleneck_group chose before
+ *          uad_bottleneck_fused_ok refused, i.e. the split the slice rule was tested against), 4 dynamic LDS bytes of the forward kernel, 5 ... of the backward kernel (0 when
+ *          unfused; the cap is 150 KiB), 6 64-sample chunks the fused parameter-gradient kernel stages at this batch (n, 2n inside a ceVAE handle), 7 rows in
+ *          the last chunk, 8 largest filter-gradient slab floats any of the four bottleneck filter-gradient GEMMs needs at this batch, 9 ... allocated per slot,
+ *          10 largest scratch floats any of the bottleneck's bias column sums needs at this batch (row chunks x columns; 0 when every sum is one chunk, which
+ *          writes its output directly), 11 ... allocated.  8 - 11 are reported on every route: UAD_NO_FUSED_BOTT / _WGRAD move a handle onto the GEMMs. */
 int uad_debug_plan(uad_model_t* m, int side, int layer, int kind, int n, long long* out);
 
 /* per-launch-group HIP-event profiler (bench.py's roofline leg).  While enabled, every launch group of

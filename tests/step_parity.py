@@ -1,5 +1,6 @@
 """One whole step of a VAE-family handle against the fp64 oracle, flip-aware -- the body test_gpu_shapes.py (ragged batches over the planner's
-paths) and test_gpu_handle_reuse.py (one handle stepped through a batch sequence) share.
+paths), test_gpu_handle_reuse.py (one handle stepped through a batch sequence) and test_gpu_bottleneck.py (latent widths and intermediate
+resolutions over the dense bottleneck's routes) share.
 
 A Step holds the inputs of one (architecture, size, batch) and the oracle's forward on them (computed once, kept in a small module-level cache so that
 both files and every math mode reuse it).  Step.run(eng, math) does what tests/test_gpu_scale_parity.py does per mode: forward, the activation pattern
@@ -35,11 +36,11 @@ SHAPE_CASES = [('VAE', 128, 1), ('VAE', 128, 7), ('VAE', 128, 33), ('AE', 128, 6
 REUSE_CASES = [('VAE', 128, 64, (64, 33, 1, 64, 7, 64)), ('ceVAE', 128, 16, (16, 9, 16)), ('GMVAE_spatial', 256, 16, (16, 5, 16)), ('AE', 32, 80, (80, 40, 64))]
 
 
-def make_engine(arch, h, max_batch):
+def make_engine(arch, h, max_batch, zdim=128, inter=8):
     from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
     if arch == 'GMVAE_spatial':
-        return Engine(arch, h, h, 1, 8, max_batch=max_batch, dim_c=9, dim_z=1, dim_w=1, c_lambda=1.0)
-    return Engine(arch, h, h, 1, 8, 128, max_batch=max_batch)
+        return Engine(arch, h, h, 1, inter, max_batch=max_batch, dim_c=9, dim_z=1, dim_w=1, c_lambda=1.0)
+    return Engine(arch, h, h, 1, inter, zdim, max_batch=max_batch)
 
 
 def _f64(d):
@@ -64,26 +65,26 @@ class Result:
 
 
 class Step:
-    def __init__(self, arch, h, n):
-        self.arch, self.h, self.n = arch, h, n
-        self.n_pool = int(np.log2(h // 8))
-        self.tag = f'{arch} {h}x{h} n={n}'
-        zdim, flat = 128, 8 * 8 * (min(32 << (self.n_pool - 1), 128) // 8)
+    def __init__(self, arch, h, n, zdim=128, inter=8):
+        self.arch, self.h, self.n, self.zdim, self.inter = arch, h, n, zdim, inter
+        self.n_pool = int(np.log2(h // inter))
+        self.tag = f'{arch} {h}x{h} n={n}' + ('' if (zdim, inter) == (128, 8) else f' zdim={zdim} inter={inter}')
+        flat = inter * inter * (min(32 << (self.n_pool - 1), 128) // 8)
         self.x = ovae.synthetic_slices(n, h, h, seed=n, dtype=np.float32)
         rng = np.random.default_rng(n)
         mrng = np.random.default_rng(1000 + n)      # the dropout masks draw from a stream of their own: slices, eps and x_ce stay what the sweep always fed
         if arch == 'GMVAE_spatial':
-            self.m = og.GMVAE(h, h, 1, 8, 9, 1, 1, 1.0)
+            self.m = og.GMVAE(h, h, 1, inter, 9, 1, 1, 1.0)
             self.p32 = og.init_params(self.m.spec, seed=7, dtype=np.float32, perturb=True)
-            self.e_w = rng.standard_normal((n, 8, 8, 1)).astype(np.float32)
-            self.e_z = rng.standard_normal((n, 8, 8, 1)).astype(np.float32)
+            self.e_w = rng.standard_normal((n, inter, inter, 1)).astype(np.float32)
+            self.e_z = rng.standard_normal((n, inter, inter, 1)).astype(np.float32)
             self.bn = {'enc': self.m.bn[:self.n_pool], 'dec_in': self.m.bn[self.n_pool], 'dec': self.m.bn[self.n_pool + 1:]}
             self.p64, self.x64 = _f64(self.p32), self.x.astype(np.float64)
             self.out, self.cache = self.m.forward(self.p64, self.x64, self.e_w.astype(np.float64), self.e_z.astype(np.float64))
             self.ls = self.m.losses(self.x64, self.out)
             self.n_bn = sum(v.size for k, v in self.cache.items() if 'bn' in k)
             return
-        self.m = ovae.CeVAE(h, h, 1, 8, zdim) if arch == 'ceVAE' else ovae.Model(arch, h, h, 1, 8, zdim)
+        self.m = ovae.CeVAE(h, h, 1, inter, zdim) if arch == 'ceVAE' else ovae.Model(arch, h, h, 1, inter, zdim)
         self.p32 = ovae.init_params(self.m.spec, seed=11, dtype=np.float32, perturb=True)
         self.eps = rng.standard_normal((n, zdim)).astype(np.float32)
         self.x_ce = self.x * (rng.random(self.x.shape) > 0.05).astype(np.float32) if arch == 'ceVAE' else None
@@ -139,7 +140,7 @@ class Step:
         return device_activation_pattern(eng, self.p32, self.x, got['x_hat'], self.cache, np_, self.bn, math=math, xhat_oracle=self.out['x_hat'])
 
     def check_forward(self, got, math):
-        """reconstruction(s) and scalars against the oracle; returns {quantity: relative error}"""
+        """reconstruction(s), latent outputs and scalars against the oracle; returns {quantity: relative error}"""
         tol, err = TOL[math], {}
         sc = got['scalars'].cpu().numpy()
         if self.arch == 'GMVAE_spatial':
@@ -156,6 +157,11 @@ class Step:
                 table = ((0, 'reconstructionLoss'), (1, 'kl'), (2, 'loss'))
             else:
                 table = ((0, 'reconstructionLoss'), (2, 'loss'))
+        if self.arch != 'GMVAE_spatial':
+            # the latent outputs the caller receives (ceVAE: the VAE branch's): the fused bottleneck stores them from one workgroup's first k-group only, the
+            # unfused chain from its reparam kernel; nothing downstream reads z_log_sigma back, so only this comparison holds it
+            for key in (('z',) if self.arch == 'AE' else ('z_mu', 'z_log_sigma', 'z_sigma')):
+                err[key] = assert_close(got[key].cpu().numpy(), self.out[key], tol=tol, name=f'{key} ({math})')
         for idx, key in table:
             ref = float(self.ls[key])
             err[key] = abs(float(sc[idx]) - ref) / max(abs(ref), floor, 1e-30)
@@ -211,16 +217,16 @@ class Step:
 _STEPS = OrderedDict()
 
 
-def step(arch, h, n, keep=5):
-    """The Step of (arch, h, n), its oracle forward computed once: the two files and the three math modes share it (a few stay cached: an oracle cache of
-    64 slices at 128 x 128 holds every layer's fp64 activations, ~1.5 GB)."""
-    key = (arch, h, n)
+def step(arch, h, n, keep=5, zdim=128, inter=8):
+    """The Step of (arch, h, n[, zdim, inter]), its oracle forward computed once: the test files and the three math modes share it (a few stay cached: an
+    oracle cache of 64 slices at 128 x 128 holds every layer's fp64 activations, ~1.5 GB)."""
+    key = (arch, h, n) if (zdim, inter) == (128, 8) else (arch, h, n, zdim, inter)
     if key in _STEPS:
         _STEPS.move_to_end(key)
         return _STEPS[key]
     while len(_STEPS) >= keep:
         _STEPS.popitem(last=False)
-    _STEPS[key] = Step(arch, h, n)
+    _STEPS[key] = Step(arch, h, n, zdim, inter)
     return _STEPS[key]
 
 
@@ -231,12 +237,21 @@ def planned_blocks(eng):
     return [(side, i, k) for side, first in (('enc', 1), ('dec', 0)) for i in range(first, n_pool) for k in 'FDW']
 
 
-def check_capacity(eng, n, shrink=1, kinds='FDW'):
+def has_bottleneck(eng):
+    return eng.arch in ('AE', 'VAE', 'ceVAE')
+
+
+def check_capacity(eng, n, shrink=1, kinds='FDWB'):
     """Every buffer uad_create sized at max_batch holds what the plan at batch n asks for: filter-gradient slabs (W, the first layer's included), BN column
     partials (data gradients), slab workspace (F / D).  The last holds by construction -- plan_gemm refuses a split whose slabs exceed the capacity it is given,
     and the handle gives it the allocated size -- and is asserted as the planner's own invariant; the first two are what uad_create has to get right.
-    NOT covered: the slabs of the bottleneck's dense / 1x1 filter gradients (generic kernel, unfused bottleneck only), which uad_create sizes by the same loop but
-    uad_debug_plan does not report.  shrink: divide the capacities (the test's own proof that it can fail); kinds: which launches to check."""
+    B: the dense bottleneck's row (AE / VAE / ceVAE) -- the slabs of its four dense / 1x1 filter gradients (generic kernel) and the scratch of its bias column
+    sums, whichever route the handle takes (the GEMMs are one environment switch away on every handle).
+    shrink: divide the capacities (the test's own proof that it can fail); kinds: which launches to check."""
+    if 'B' in kinds and has_bottleneck(eng):
+        p = eng.debug_plan('bott', 0, 'B', n)
+        assert p['need'] <= p['cap'] // shrink, f'{eng.arch} max_batch {eng.max_batch} {eng.math}: the bottleneck at n = {n} needs {p["need"]} filter-gradient slab floats, allocated {p["cap"] // shrink}: {p}'
+        assert p['cs_need'] <= p['cs_cap'] // shrink, f'{eng.arch} max_batch {eng.max_batch} {eng.math}: the bottleneck at n = {n} needs {p["cs_need"]} column-sum scratch floats, allocated {p["cs_cap"] // shrink}: {p}'
     for side, layer, kind in [('enc', 0, 'W')] + planned_blocks(eng):
         if kind not in kinds:
             continue

@@ -2,6 +2,8 @@
 runs the whole-model parity tests of tests/test_gpu_model.py (forward, every gradient tensor, Adam trajectory vs the oracle) in a fresh
 interpreter with the switch set:
   UAD_BOTT_Q1              one workgroup per sample in the fused bottleneck kernels instead of a group of four
+  UAD_NO_FUSED_BOTT        dense bottleneck as the chain of generic 1x1 / dense launches + reparam kernels + GEMM parameter gradients and column sums (n = 80 included:
+                           the ragged batch past the 64-row tiles) instead of the fused per-sample kernels
   UAD_NO_FUSED_BOTT_WGRAD  bottleneck parameter gradients as batched GEMMs + column sums instead of bottleneck_wgrad_kernel
   UAD_NO_FIRST32           generic first-layer kernels instead of conv_first_fwd32 / conv_first_wgrad32
   UAD_NO_SIDE_PACK         weight repack on the caller's stream inside the next forward instead of on the side stream after the optimizer step
@@ -31,7 +33,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize('knob', ['UAD_BOTT_Q1', 'UAD_NO_FUSED_BOTT_WGRAD', 'UAD_NO_FIRST32', 'UAD_NO_SIDE_PACK', 'UAD_NO_INKERNEL_SPLITK',
+@pytest.mark.parametrize('knob', ['UAD_BOTT_Q1', 'UAD_NO_FUSED_BOTT', 'UAD_NO_FUSED_BOTT_WGRAD', 'UAD_NO_FIRST32', 'UAD_NO_SIDE_PACK', 'UAD_NO_INKERNEL_SPLITK',
                                   'UAD_NO_D16S', 'UAD_NO_D16S_T16', 'UAD_NO_REDUCE4', 'UAD_NO_TAIL_SPLIT', 'UAD_NO_ANYORDER', 'UAD_NO_FUSED_FINAL_F32', 'UAD_NO_PACK_HEAD', 'UAD_NO_W5_DB',
                                   'UAD_SPATIAL_MIN_WGS=256'])
 def test_model_parity_with_switch(knob):

@@ -14,7 +14,8 @@ except Exception:
     pass
 
 
-@pytest.mark.parametrize('h,zdim,n,math', [(64, 32, 2, 'f32'), (128, 128, 4, 'bf16x3')])
+@pytest.mark.parametrize('h,zdim,n,math', [(64, 32, 2, 'f32'), (128, 128, 4, 'bf16x3'),
+                                           (64, 48, 2, 'f32')])      # zDim 48: the unfused bottleneck chain, data gradients only, per-sample scale
 def test_vae_restore_step_matches_oracle(h, zdim, n, math):
     from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
     m = ovae.Model('VAE', h, h, 1, 8, zdim)
@@ -23,6 +24,7 @@ def test_vae_restore_step_matches_oracle(h, zdim, n, math):
     rng = np.random.default_rng(6)
     eng = Engine('VAE', h, h, 1, 8, zdim, max_batch=n, math=math)
     eng.set_params(p)
+    assert eng.debug_plan('bott', 0, 'B', n)['fused'] == (0 if zdim == 48 else 1)      # the zDim 48 case is here for the unfused bottleneck chain
     sentinel = np.full(eng.nparams, 3.0, np.float32)
     eng.set_buffer_host(_lib.BUF_GRADS, sentinel)
     xr = torch.from_numpy(x.astype(np.float32)).cuda()

@@ -120,9 +120,10 @@ __device__ __forceinline__ void group_exchange(const UadBottArgs& a, int n, int 
 // out[col] (col in this workgroup's slice [c0, c0 + NC) of a row-major [K][ld] matrix, coalesced over col) = sum_k x[k] * W[k][c0 + col]:
 // NT threads = G k-groups x CP columns per pass (G > 1 when the slice is narrower than the workgroup), 16 independent row loads in
 // flight per thread, group partials through s_part.  fin(col, sum) runs on the k-group-0 thread of each column.
+__host__ __device__ constexpr int slice_kgroups(int NC) { return NC < NT ? NT / NC : 1; }
 template <typename Fin>
 __device__ __forceinline__ void gemv_slice(const float* __restrict__ W, size_t ld, int c0, int NC, const float* x, int K, float* s_part, int tid, Fin fin) {
-    const int G = NC < NT ? NT / NC : 1;
+    const int G = slice_kgroups(NC);
     const int CP = NT / G;
     const int kg = tid / CP, cl = tid % CP;
     const int kper = K / G;
@@ -412,28 +413,28 @@ __global__ void __launch_bounds__(NT) bottleneck_bwd_kernel(const UadBottArgs a)
 //                             backward kernel leaves its positions' share (it has dcb, dflat and the c_enc rows at hand), this kernel
 //                             sums the shares.
 // Deterministic: every sum runs in a fixed order.
-constexpr int WG_NT = 256, WG_TI = 32, WG_TJ = 64;
+constexpr int WG_NT = 256, WG_TI = 32, WG_TJ = 64, WG_TS = 64;      // threads, output tile, samples staged per chunk
 
 __device__ __forceinline__ void wgrad_dense_tile(const float* __restrict__ A, int I, const float* __restrict__ B, int J, int n, int ti, int tj,
                                                  float* __restrict__ out, float* __restrict__ dbias, float* sm) {
     // out[i][j] = sum_s A[s][i] * B[s][j] for the tile (ti, tj); dbias[j] = sum_s B[s][j] (written by the ti == 0 tiles)
-    float* sA = sm;                      // [64][WG_TI]
-    float* sB = sm + 64 * WG_TI;         // [64][WG_TJ]
+    float* sA = sm;                      // [WG_TS][WG_TI]
+    float* sB = sm + WG_TS * WG_TI;         // [WG_TS][WG_TJ]
     const int tid = threadIdx.x;
     const int i0 = ti * WG_TI, j0 = tj * WG_TJ;
     const int ip = tid / 16, jq = tid % 16;            // this thread: rows 2*ip, 2*ip+1; columns 4*jq .. 4*jq+3
     float acc[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     float bsum = 0.f;
-    for (int s0 = 0; s0 < n; s0 += 64) {
-        const int ns = min(64, n - s0);
+    for (int s0 = 0; s0 < n; s0 += WG_TS) {
+        const int ns = min(WG_TS, n - s0);
         __syncthreads();
-        for (int e = tid; e < 64 * WG_TI / 4; e += WG_NT) {
+        for (int e = tid; e < WG_TS * WG_TI / 4; e += WG_NT) {
             const int r = e / (WG_TI / 4), c4 = e % (WG_TI / 4);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (r < ns) v = *reinterpret_cast<const float4*>(A + (size_t)(s0 + r) * I + i0 + c4 * 4);
             *reinterpret_cast<float4*>(sA + r * WG_TI + c4 * 4) = v;
         }
-        for (int e = tid; e < 64 * WG_TJ / 4; e += WG_NT) {
+        for (int e = tid; e < WG_TS * WG_TJ / 4; e += WG_NT) {
             const int r = e / (WG_TJ / 4), c4 = e % (WG_TJ / 4);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (r < ns) v = *reinterpret_cast<const float4*>(B + (size_t)(s0 + r) * J + j0 + c4 * 4);
@@ -441,7 +442,7 @@ __device__ __forceinline__ void wgrad_dense_tile(const float* __restrict__ A, in
         }
         __syncthreads();
 #pragma unroll 8
-        for (int r = 0; r < 64; ++r) {
+        for (int r = 0; r < WG_TS; ++r) {
             const float2 a2 = *reinterpret_cast<const float2*>(sA + r * WG_TI + 2 * ip);
             const float4 b4 = *reinterpret_cast<const float4*>(sB + r * WG_TJ + 4 * jq);
             acc[0][0] = fmaf(a2.x, b4.x, acc[0][0]); acc[0][1] = fmaf(a2.x, b4.y, acc[0][1]);
@@ -450,7 +451,7 @@ __device__ __forceinline__ void wgrad_dense_tile(const float* __restrict__ A, in
             acc[1][2] = fmaf(a2.y, b4.z, acc[1][2]); acc[1][3] = fmaf(a2.y, b4.w, acc[1][3]);
         }
         if (ti == 0 && dbias && tid < WG_TJ)
-            for (int r = 0; r < 64; ++r) bsum += sB[r * WG_TJ + tid];
+            for (int r = 0; r < WG_TS; ++r) bsum += sB[r * WG_TJ + tid];
     }
 #pragma unroll
     for (int e = 0; e < 2; ++e)
@@ -529,6 +530,8 @@ int uad_bottleneck_group(const UadBottArgs& a) {
     return slice_ok ? Q : 1;
 }
 int uad_bottleneck_colpart_rows(const UadBottArgs& a, int n) { return n * uad_bottleneck_group(a); }
+// k-groups of gemv_slice over one workgroup's feature slice (tests: uad_debug_plan)
+int uad_bottleneck_slice_kgroups(const UadBottArgs& a) { return slice_kgroups(a.npos / uad_bottleneck_group(a) * a.cmid); }
 size_t uad_bottleneck_lds_bytes(const UadBottArgs& a, bool bwd) {
     const int Q = uad_bottleneck_group(a);
     const size_t PC = (size_t)a.npos / Q * a.cenc, F = (size_t)a.npos / Q * a.cmid, CM = (size_t)a.cenc * a.cmid;
@@ -585,12 +588,13 @@ bool uad_bottleneck_wgrad_ok(const UadBottWgradArgs& a) {
     return a.part && a.nparts > 0 && a.zdim % WG_TJ == 0 && F % WG_TJ == 0;
 }
 size_t uad_bottleneck_wgrad_part_floats(const UadBottWgradArgs& a) { return (size_t)2 * a.cenc * a.cmid + a.cmid; }
+int uad_bottleneck_wgrad_chunk_rows() { return WG_TS; }
 void uad_launch_bottleneck_wgrad(const UadBottWgradArgs& a, hipStream_t st) {
     const int Z = a.zdim, F = a.npos * a.cmid;
     const int tiles_d = (Z / WG_TI) * (F / WG_TJ), tiles_h = (F / WG_TI) * (Z / WG_TJ);
     const int PW = (int)uad_bottleneck_wgrad_part_floats(a);
     const int grid = tiles_d + tiles_h * (a.dls ? 2 : 1) + (PW + 63) / 64;
-    hipLaunchKernelGGL(bottleneck_wgrad_kernel, dim3(grid), dim3(WG_NT), (size_t)64 * (WG_TI + WG_TJ) * sizeof(float), st, a);
+    hipLaunchKernelGGL(bottleneck_wgrad_kernel, dim3(grid), dim3(WG_NT), (size_t)WG_TS * (WG_TI + WG_TJ) * sizeof(float), st, a);
 }
 void uad_launch_transpose(const float* const* in, const int* R, const int* C, float* const* out, int njobs, hipStream_t st) {
     TransposeJobs jb;

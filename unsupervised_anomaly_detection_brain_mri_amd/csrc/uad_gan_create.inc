@@ -178,7 +178,7 @@ static int create_resnet(const uad_gan_config_t* cfg, uad_gan_t** out) {
         m->ws.floats = need; m->ws.ptr = nullptr; m->ws.counters = nullptr; m->ws.ncounters = 0;      // no in-kernel split-K reduction on this handle
         ALLOC(m->ws.ptr, need, nullptr);
     }
-    ALLOC(m->colscratch, 64 * 1024, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
+    ALLOC(m->colscratch, kUadColsumScratchFloats, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
     ALLOC(m->redpart, 1024, nullptr); ALLOC(m->raw, 16, "raw"); ALLOC(m->scalars_own, 16, nullptr);
     ALLOC(m->finpart, (size_t)1024 * 520, nullptr);
 #undef ALLOC
@@ -277,7 +277,7 @@ static int create_zimmerer(const uad_gan_config_t* cfg, uad_gan_t** out) {
         m->ws.floats = need; m->ws.ptr = nullptr; m->ws.counters = nullptr; m->ws.ncounters = 0;      // no in-kernel split-K reduction on this handle
         ALLOC(m->ws.ptr, need, nullptr);
     }
-    size_t cs = 64 * 1024;
+    size_t cs = kUadColsumScratchFloats;
     { const size_t v = uad_colsum_scratch_floats((int)NB, m->flat); if (v > cs) cs = v; }
     ALLOC(m->colscratch, cs, nullptr);
     ALLOC(m->redpart, 1024, nullptr); ALLOC(m->raw, 16, "raw"); ALLOC(m->scalars_own, 16, nullptr);
@@ -402,7 +402,7 @@ static int create_you(const uad_gan_config_t* cfg, uad_gan_t** out) {
         m->ws.floats = need; m->ws.ptr = nullptr; m->ws.counters = nullptr; m->ws.ncounters = 0;      // no in-kernel split-K reduction on this handle
         ALLOC(m->ws.ptr, need, nullptr);
     }
-    ALLOC(m->colscratch, 64 * 1024, nullptr);
+    ALLOC(m->colscratch, kUadColsumScratchFloats, nullptr);
     ALLOC(m->redpart, 1024, nullptr); ALLOC(m->raw, 16, "raw"); ALLOC(m->scalars_own, 16, nullptr);
 #undef ALLOC
     if (rc != UAD_OK) { uad_gan_destroy(m); return rc; }
@@ -556,7 +556,7 @@ static int create_chen(const uad_gan_config_t* cfg, uad_gan_t** out) {
         m->ws.floats = need; m->ws.ptr = nullptr; m->ws.counters = nullptr; m->ws.ncounters = 0;      // no in-kernel split-K reduction on this handle
         ALLOC(m->ws.ptr, need, nullptr);
     }
-    ALLOC(m->colscratch, 64 * 1024, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
+    ALLOC(m->colscratch, kUadColsumScratchFloats, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
     ALLOC(m->redpart, 1024, nullptr); ALLOC(m->raw, 16, "raw"); ALLOC(m->scalars_own, 16, nullptr);
     ALLOC(m->finpart, (size_t)1024 * 520, nullptr);
 #undef ALLOC
@@ -722,7 +722,7 @@ static int create_aae(const uad_gan_config_t* cfg, uad_gan_t** out) {
         m->ws.floats = need; m->ws.ptr = nullptr; m->ws.counters = nullptr; m->ws.ncounters = 0;      // no in-kernel split-K reduction on this handle
         ALLOC(m->ws.ptr, need, nullptr);
     }
-    ALLOC(m->colscratch, 64 * 1024, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
+    ALLOC(m->colscratch, kUadColsumScratchFloats, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
     ALLOC(m->redpart, 1024, nullptr); ALLOC(m->raw, 16, "raw"); ALLOC(m->scalars_own, 16, nullptr);
     ALLOC(m->finpart, (size_t)1024 * 65, nullptr);
 #undef ALLOC
@@ -913,7 +913,7 @@ int uad_gan_create(const uad_gan_config_t* cfg, uad_gan_t** out) {
         m->ws.floats = need; m->ws.ptr = nullptr; m->ws.counters = nullptr; m->ws.ncounters = 0;      // no in-kernel split-K reduction on this handle
         ALLOC(m->ws.ptr, need, nullptr);
     }
-    ALLOC(m->colscratch, 64 * 1024, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
+    ALLOC(m->colscratch, kUadColsumScratchFloats, nullptr); ALLOC(m->colpart, (size_t)kBnBwdBlocks * 2 * 128, nullptr);
     ALLOC(m->redpart, 1024, nullptr); ALLOC(m->raw, 16, "raw"); ALLOC(m->scalars_own, 16, nullptr);
     ALLOC(m->finpart, (size_t)1024 * 65, nullptr);
 #undef ALLOC

@@ -145,6 +145,8 @@ size_t uad_bn_grad_finalize_scratch_floats(int C);
 void uad_launch_final_gradfin(const float* red, int C, const float* gamma, float rstd, float* dwf, float* dbf, float* dgamma, float* dbeta,
                               float* dbias, hipStream_t st);
 // out[c] = sum_rows g[row][c]
+// scratch: kUadColsumScratchFloats floats (what every handle allocates; the row chunks of a sum are capped so that their partials fit it)
+constexpr size_t kUadColsumScratchFloats = 64 * 1024;
 void uad_launch_colsum(const float* g, int rows, int C, float* out, float* scratch, hipStream_t st);
 size_t uad_colsum_scratch_floats(int rows, int C);
 
@@ -222,6 +224,7 @@ size_t uad_bottleneck_lds_bytes(const UadBottArgs& a, bool bwd);
 bool uad_bottleneck_fused_ok(const UadBottArgs& a);
 int uad_bottleneck_group(const UadBottArgs& a);                  // workgroups per sample (1 or 4)
 int uad_bottleneck_colpart_rows(const UadBottArgs& a, int n);    // rows of colpart [rows][2][cenc] the backward writes
+int uad_bottleneck_slice_kgroups(const UadBottArgs& a);          // k-groups the threads of a workgroup form over its feature slice (1 when the slice is >= 1024 wide)
 void uad_launch_bottleneck_fwd(const UadBottArgs& a, int n, hipStream_t st);
 void uad_launch_bottleneck_bwd(const UadBottArgs& a, int n, hipStream_t st);
 // every parameter gradient of the dense bottleneck in one launch (uad_bott.hip); dls / gWsg / gbsg null: AE
@@ -236,6 +239,7 @@ struct UadBottWgradArgs {
 };
 bool uad_bottleneck_wgrad_ok(const UadBottWgradArgs& a);
 size_t uad_bottleneck_wgrad_part_floats(const UadBottWgradArgs& a);
+int uad_bottleneck_wgrad_chunk_rows();                           // samples the wgrad kernel stages per pass over the batch
 void uad_launch_bottleneck_wgrad(const UadBottWgradArgs& a, hipStream_t st);
 // out_i[c][r] = in_i[r][c] for up to 3 matrices in one launch
 void uad_launch_transpose(const float* const* in, const int* R, const int* C, float* const* out, int njobs, hipStream_t st);

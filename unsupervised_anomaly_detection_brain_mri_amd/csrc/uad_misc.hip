@@ -1094,7 +1094,7 @@ void uad_launch_bn_grad_finalize(const float* colpart, int T, int C, const float
 static inline int colsum_chunks(int rows, int C) {
     static const int cap_env = getenv("UAD_COLSUM_CHUNKS") ? atoi(getenv("UAD_COLSUM_CHUNKS")) : 0;
     int cap = cap_env > 0 ? cap_env : 1024;
-    const int fit = 65536 / (C < 1 ? 1 : C);
+    const int fit = (int)kUadColsumScratchFloats / (C < 1 ? 1 : C);
     if (cap > fit) cap = fit;
     if (cap < 1) cap = 1;
     int ch = (rows + 255) / 256;

@@ -115,7 +115,7 @@ struct uad_model {
     float *g_small[6];                // d_cb-side temporaries: dd, dz, dmu_raw, dls_raw, dflat, dflat2
     // scratch
     float *colpart, *wpartial, *colscratch, *red_partial, *rec_partial, *rec_ps, *scalars_own;
-    size_t colpart_cap, wpartial_cap;
+    size_t colpart_cap, wpartial_cap, colscratch_cap;
     // state of the last forward
     int last_n, last_nuser;            // samples inside the handle / samples the caller passed
     uad_io_t last_io;
@@ -265,6 +265,41 @@ UadBottArgs bott_args(uad_model* m, const uad_io_t& io, const float* mask_dec, i
 
 UadConvDesc dense_desc(int n, int in, int out) { return UadConvDesc{n, 1, 1, in, 1, 1, out, 1, 1, 0}; }
 UadConvDesc conv1x1_desc(int n, int h, int w, int cin, int cout) { return UadConvDesc{n, h, w, cin, h, w, cout, 1, 1, 0}; }
+
+// the four GEMM shapes of the dense bottleneck at n rows: conv2d_1 (r), dense_dec (dec), dense_mu / _sigma / _z (in), conv2d (b)
+struct BottDescs { UadConvDesc r, dec, in, b; };
+BottDescs bott_descs(const uad_model* m, int n) {
+    const int ir = m->cfg.inter_res, zd = m->cfg.zdim;
+    return BottDescs{conv1x1_desc(n, ir, ir, m->cmid, m->cenc), dense_desc(n, zd, m->flat), dense_desc(n, m->flat, zd), conv1x1_desc(n, ir, ir, m->cenc, m->cmid)};
+}
+// its bias gradients as column sums [rows][C]: dense_dec, the latent heads, conv2d
+enum { BCS_DEC = 0, BCS_HEAD = 1, BCS_CONV = 2, BCS_COUNT = 3 };
+void bott_colsum_shape(const uad_model* m, int n, int which, int* rows, int* C) {
+    const int ir = m->cfg.inter_res;
+    *rows = which == BCS_CONV ? n * ir * ir : n;
+    *C = which == BCS_DEC ? m->flat : which == BCS_HEAD ? m->cfg.zdim : m->cmid;
+}
+void bott_colsum(uad_model* m, int n, int which, const float* g, long long grad_off, hipStream_t sd) {
+    int rows, C;
+    bott_colsum_shape(m, n, which, &rows, &C);
+    uad_launch_colsum(g, rows, C, m->grads + grad_off, m->colscratch, sd);
+}
+// arguments of the one-launch parameter gradients of the fused bottleneck (n rows; ba: the backward launch's arguments)
+UadBottWgradArgs bott_wgrad_args(uad_model* m, const UadBottArgs& ba, int n) {
+    const bool vae = m->sgw >= 0;
+    const ConvLayer& EL = m->enc.back();
+    UadBottWgradArgs wa;
+    memset(&wa, 0, sizeof wa);
+    wa.n = n; wa.cenc = m->cenc; wa.cmid = m->cmid; wa.npos = m->cfg.inter_res * m->cfg.inter_res; wa.zdim = m->cfg.zdim; wa.alpha = kLrelu; wa.mult = 1.0f / sqrtf(1.0f + kBnEps);
+    wa.z = m->z; wa.dd = m->g_small[0]; wa.t = m->t; wa.dmu = vae ? m->g_small[2] : m->g_small[1]; wa.dls = vae ? m->g_small[3] : nullptr;
+    wa.c_enc = EL.c; wa.scale = m->params + EL.gamma; wa.shift = m->params + EL.beta;
+    wa.dflat = m->g_small[4]; wa.dvec = m->dvec; wa.dcb = m->dcb_keep;
+    wa.gWd = m->grads + m->dw; wa.gbd = m->grads + m->db; wa.gWmu = m->grads + m->muw; wa.gbmu = m->grads + m->mub;
+    if (vae) { wa.gWsg = m->grads + m->sgw; wa.gbsg = m->grads + m->sgb; }
+    wa.gWb = m->grads + m->bw; wa.gbb = m->grads + m->bb; wa.gWr = m->grads + m->rw;
+    wa.part = m->bott_wpart; wa.nparts = uad_bottleneck_colpart_rows(ba, n);
+    return wa;
+}
 
 int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
@@ -484,8 +519,8 @@ int uad_create(const uad_config_t* cfg, uad_model_t** out) {
     for (size_t i = 1; i < m->enc.size(); ++i) wp_need(m->enc[i].d);
     for (auto& L : m->dec) wp_need(L.d);
     if (!gm && !sp) {
-        wp_need(conv1x1_desc(1, ir, ir, m->cenc, m->cmid)); wp_need(conv1x1_desc(1, ir, ir, m->cmid, m->cenc));
-        wp_need(dense_desc(1, m->flat, cfg->zdim)); wp_need(dense_desc(1, cfg->zdim, m->flat));
+        const BottDescs bd = bott_descs(m, 1);
+        wp_need(bd.b); wp_need(bd.r); wp_need(bd.in); wp_need(bd.dec);
     }
     { UadConvDesc d0 = m->enc[0].d; for (size_t nb = m->nmul; nb <= NB; nb += m->nmul) { d0.N = (int)nb; size_t v = uad_conv_first_wgrad_partial_floats(d0); if (v > wp) wp = v; } }      // (rows per block grow with the batch: not monotone either)
     m->wpartial_cap = wp; ALLOC(m->wpartial, wp);
@@ -506,7 +541,7 @@ int uad_create(const uad_config_t* cfg, uad_model_t** out) {
         // arrival counters of the in-kernel split-K reduction: one per (spatial tile, column block) of a split launch
         { float* c = nullptr; m->ws.ncounters = 16384; ALLOC(c, m->ws.ncounters); m->ws.counters = reinterpret_cast<unsigned*>(c); }
     }
-    ALLOC(m->colscratch, 64 * 1024);
+    m->colscratch_cap = kUadColsumScratchFloats; ALLOC(m->colscratch, m->colscratch_cap);
     const int bps = uad_final_blocks_per_sample(H, Wd);
     ALLOC(m->red_partial, NB * bps * (3 * cin + 1)); ALLOC(m->rec_partial, NB * bps);
     ALLOC(m->rec_ps, NB); ALLOC(m->scalars_own, 8);
@@ -1038,7 +1073,7 @@ static int backward_bottleneck(uad_model* m, hipStream_t st, bool join_now) {
     const bool vae = m->cfg.arch != UAD_ARCH_AE;
     const bool cevae = m->cfg.arch == UAD_ARCH_CEVAE;
     const bool pg = !m->data_only;
-    const int ir = m->cfg.inter_res, zd = m->cfg.zdim;
+    const int zd = m->cfg.zdim;
     const float rstd = 1.0f / sqrtf(1.0f + kBnEps);
     const uad_io_t& io = m->last_io;
     hipStream_t sd = m->side;
@@ -1050,10 +1085,8 @@ static int backward_bottleneck(uad_model* m, hipStream_t st, bool join_now) {
     float* dflat = m->g_small[4];
     float* cp = m->cp_slot[15];
     float* wp = m->wp_slot[15];                 // SIDE-only slab scratch of the bottleneck weight gradients
-    const UadConvDesc d_r = conv1x1_desc(n, ir, ir, m->cmid, m->cenc);
-    const UadConvDesc d_dec = dense_desc(n, zd, m->flat);
-    const UadConvDesc d_in = dense_desc(n, m->flat, zd);
-    const UadConvDesc d_b = conv1x1_desc(n, ir, ir, m->cenc, m->cmid);
+    const BottDescs bd = bott_descs(m, n);
+    const UadConvDesc d_r = bd.r, d_dec = bd.dec, d_in = bd.in, d_b = bd.b;
     const ConvLayer& EL = m->enc.back();
     {
         UadBottArgs ba = bott_args(m, io, m->mask_dec_eff, nu);
@@ -1067,34 +1100,24 @@ static int backward_bottleneck(uad_model* m, hipStream_t st, bool join_now) {
             ba.epoch = ++m->bott_epoch;
             { PROF("bott.bwd"); uad_launch_bottleneck_bwd(ba, n, st); }
             if (pg) edge(m, st, sd);
-            UadBottWgradArgs wa;
-            memset(&wa, 0, sizeof wa);
-            wa.n = n; wa.cenc = m->cenc; wa.cmid = m->cmid; wa.npos = ir * ir; wa.zdim = zd; wa.alpha = kLrelu; wa.mult = rstd;
-            wa.z = m->z; wa.dd = dd; wa.t = m->t; wa.dmu = vae ? dmu : dz; wa.dls = vae ? dls : nullptr;
-            wa.c_enc = EL.c; wa.scale = P(m, EL.gamma); wa.shift = P(m, EL.beta);
-            wa.dflat = dflat; wa.dvec = m->dvec; wa.dcb = m->dcb_keep;
-            wa.gWd = Gr(m, m->dw); wa.gbd = Gr(m, m->db); wa.gWmu = Gr(m, m->muw); wa.gbmu = Gr(m, m->mub);
-            if (vae) { wa.gWsg = Gr(m, m->sgw); wa.gbsg = Gr(m, m->sgb); }
-            wa.gWb = Gr(m, m->bw); wa.gbb = Gr(m, m->bb); wa.gWr = Gr(m, m->rw);
-            wa.part = m->bott_wpart; wa.nparts = uad_bottleneck_colpart_rows(ba, n);
-            if (pg && uad_bottleneck_wgrad_ok(wa)) {
+            if (pg && uad_bottleneck_wgrad_ok(bott_wgrad_args(m, ba, n))) {
                 // SIDE: every parameter gradient of the segment in one launch (+ the last encoder block's BN finalize)
                 PROF_ON("bott.wgrad", sd);
-                uad_launch_bottleneck_wgrad(wa, sd);
+                uad_launch_bottleneck_wgrad(bott_wgrad_args(m, ba, n), sd);      // (reads dd / dmu | dz / dls / dflat = g_small[0 .. 4] as named above)
                 uad_launch_bn_grad_finalize(cp, uad_bottleneck_colpart_rows(ba, n), m->cenc, P(m, EL.gamma), rstd, Gr(m, EL.gamma), Gr(m, EL.beta), Gr(m, EL.b), sd);
             } else if (pg) {
                 PROF_ON("bott.wgrad", sd);
                 uad_launch_conv_w(d_r, m->dvec, no_xform(), m->dcb_keep, no_xform(), Gr(m, m->rw), wp, sd);
                 uad_launch_conv_w(d_dec, m->z, no_xform(), dd, no_xform(), Gr(m, m->dw), wp, sd);
-                uad_launch_colsum(dd, n, m->flat, Gr(m, m->db), m->colscratch, sd);
+                bott_colsum(m, n, BCS_DEC, dd, m->db, sd);
                 uad_launch_conv_w(d_in, m->t, no_xform(), vae ? dmu : dz, no_xform(), Gr(m, m->muw), wp, sd);
-                uad_launch_colsum(vae ? dmu : dz, n, zd, Gr(m, m->mub), m->colscratch, sd);
+                bott_colsum(m, n, BCS_HEAD, vae ? dmu : dz, m->mub, sd);
                 if (vae) {
                     uad_launch_conv_w(d_in, m->t, no_xform(), dls, no_xform(), Gr(m, m->sgw), wp, sd);
-                    uad_launch_colsum(dls, n, zd, Gr(m, m->sgb), m->colscratch, sd);
+                    bott_colsum(m, n, BCS_HEAD, dls, m->sgb, sd);
                 }
                 uad_launch_conv_w(d_b, EL.c, bn_xform(m, EL.gamma, EL.beta, kLrelu), dflat, no_xform(), Gr(m, m->bw), wp, sd);
-                uad_launch_colsum(dflat, n * ir * ir, m->cmid, Gr(m, m->bb), m->colscratch, sd);
+                bott_colsum(m, n, BCS_CONV, dflat, m->bb, sd);
                 uad_launch_bn_grad_finalize(cp, uad_bottleneck_colpart_rows(ba, n), m->cenc, P(m, EL.gamma), rstd, Gr(m, EL.gamma), Gr(m, EL.beta), Gr(m, EL.b), sd);
             }
             float* tsw = m->G0; m->G0 = m->G1; m->G1 = tsw;
@@ -1111,7 +1134,7 @@ static int backward_bottleneck(uad_model* m, hipStream_t st, bool join_now) {
         edge(m, st, sd);
         if (pg) { PROF_ON("bott.wgrad", sd);
           uad_launch_conv_w(d_dec, m->z, no_xform(), dd, no_xform(), Gr(m, m->dw), wp, sd);
-          uad_launch_colsum(dd, n, m->flat, Gr(m, m->db), m->colscratch, sd); }
+          bott_colsum(m, n, BCS_DEC, dd, m->db, sd); }
         uad_launch_conv_d(d_dec, dd, no_xform(), P(m, m->dw), dz, epi_bias(nullptr, vae ? nullptr : io.mask_mu), st, nullptr, m->ws);
         if (vae) {
             uad_launch_reparam_bwd(n, nu, zd, dz, m->mu, m->sigma, io.eps, io.mask_mu, io.mask_sigma,
@@ -1119,22 +1142,22 @@ static int backward_bottleneck(uad_model* m, hipStream_t st, bool join_now) {
             edge(m, st, sd);
             if (pg) { PROF_ON("bott.wgrad", sd);
               uad_launch_conv_w(d_in, m->t, no_xform(), dmu, no_xform(), Gr(m, m->muw), wp, sd);
-              uad_launch_colsum(dmu, n, zd, Gr(m, m->mub), m->colscratch, sd);
+              bott_colsum(m, n, BCS_HEAD, dmu, m->mub, sd);
               uad_launch_conv_w(d_in, m->t, no_xform(), dls, no_xform(), Gr(m, m->sgw), wp, sd);
-              uad_launch_colsum(dls, n, zd, Gr(m, m->sgb), m->colscratch, sd); }
+              bott_colsum(m, n, BCS_HEAD, dls, m->sgb, sd); }
             uad_launch_conv_d(d_in, dmu, no_xform(), P(m, m->muw), m->g_small[5], epi_bias(nullptr), st, nullptr, m->ws);
             uad_launch_conv_d(d_in, dls, no_xform(), P(m, m->sgw), dflat, epi_bias(nullptr, nullptr, m->g_small[5]), st, nullptr, m->ws);
         } else {
             edge(m, st, sd);
             if (pg) { PROF_ON("bott.wgrad", sd);
               uad_launch_conv_w(d_in, m->t, no_xform(), dz, no_xform(), Gr(m, m->muw), wp, sd);
-              uad_launch_colsum(dz, n, zd, Gr(m, m->mub), m->colscratch, sd); }
+              bott_colsum(m, n, BCS_HEAD, dz, m->mub, sd); }
             uad_launch_conv_d(d_in, dz, no_xform(), P(m, m->muw), dflat, epi_bias(nullptr), st, nullptr, m->ws);
         }
         edge(m, st, sd);
         if (pg) { PROF_ON("bott.wgrad", sd);
           uad_launch_conv_w(d_b, EL.c, bn_xform(m, EL.gamma, EL.beta, kLrelu), dflat, no_xform(), Gr(m, m->bw), wp, sd);
-          uad_launch_colsum(dflat, n * ir * ir, m->cmid, Gr(m, m->bb), m->colscratch, sd); }
+          bott_colsum(m, n, BCS_CONV, dflat, m->bb, sd); }
         UadEpilogue e = epi_bwd(m, EL.c, EL.gamma, EL.beta, kLrelu); e.colpart = cp;
         uad_launch_conv_d(d_b, dflat, no_xform(), P(m, m->bw), m->G1, e, st, nullptr, m->ws);
     }
@@ -1453,7 +1476,8 @@ int uad_debug_buffer(uad_model_t* m, const char* name, float** ptr, long long* c
 
 // tests: the launch plan of one 5x5 block at batch n in the handle's current math mode -- nothing is launched.  side 0 = encoder block `layer` (>= 1: block 0 runs the
 // one-channel first-layer kernels), 1 = decoder block `layer`; kind 'F' / 'D' / 'W' as the launchers are named (encoder: F forward, D data gradient; decoder: D
-// forward, F data gradient; W filter gradient).  Same decision functions, same arguments as uad_forward / uad_backward pass.
+// forward, F data gradient; W filter gradient).  Same decision functions, same arguments as uad_forward / uad_backward pass.  side 2 = the dense bottleneck
+// (layer 0, kind 'B'; fields: include/uad_hip.h).
 int uad_debug_plan(uad_model_t* m, int side, int layer, int kind, int n, long long* out) {
     if (!m || !out) return fail(UAD_ERR_INVALID, "null argument");
     if (n <= 0 || n > m->cfg.max_batch) return fail(UAD_ERR_INVALID, "batch %d outside (0, max_batch=%d]", n, m->cfg.max_batch);
@@ -1462,6 +1486,39 @@ int uad_debug_plan(uad_model_t* m, int side, int layer, int kind, int n, long lo
         for (int k = 0; k < 12; ++k) out[k] = 0;
         out[0] = 3; out[5] = -1; out[6] = -1; out[8] = (long long)uad_conv_first_wgrad_partial_floats(d0); out[9] = (long long)m->wpartial_cap; out[11] = (long long)m->colpart_cap;
         out[1] = out[8] / ((long long)d0.KS * d0.KS * d0.CB * d0.CS);
+        return UAD_OK;
+    }
+    if (side == 2) {
+        // the dense bottleneck (layer 0, kind 'B'): the route uad_forward / backward_bottleneck take at n, from the launchers' own decision functions
+        if (m->bw < 0) return fail(UAD_ERR_INVALID, "this architecture has no dense bottleneck");
+        if (layer != 0 || kind != 'B') return fail(UAD_ERR_INVALID, "bottleneck plan: layer 0, kind 'B'");
+        const int rows = n * m->nmul;
+        uad_io_t io;
+        memset(&io, 0, sizeof io);
+        const UadBottArgs ba = bott_args(m, io, nullptr, n);      // (no decision reads the batch's inputs, masks or the launch epoch)
+        const bool fused = uad_bottleneck_fused_ok(ba);
+        out[0] = fused ? 1 : 0;
+        out[1] = uad_bottleneck_group(ba);
+        out[2] = fused ? (uad_bottleneck_wgrad_ok(bott_wgrad_args(m, ba, rows)) ? 1 : 0) : -1;
+        out[3] = uad_bottleneck_slice_kgroups(ba);
+        out[4] = fused ? (long long)uad_bottleneck_lds_bytes(ba, false) : 0;
+        out[5] = fused ? (long long)uad_bottleneck_lds_bytes(ba, true) : 0;
+        const int chunk = uad_bottleneck_wgrad_chunk_rows();
+        out[6] = (rows + chunk - 1) / chunk;
+        out[7] = rows - (out[6] - 1) * chunk;
+        // the GEMM parameter gradients (unfused route, fused route without the one-launch wgrad, UAD_NO_FUSED_BOTT*): slabs in a wp_slot, bias sums through colscratch
+        const BottDescs bd = bott_descs(m, rows);
+        out[8] = 0;
+        for (const UadConvDesc& d : {bd.r, bd.dec, bd.in, bd.b}) { const long long v = (long long)uad_conv_w_partial_floats(d); if (v > out[8]) out[8] = v; }
+        out[9] = (long long)m->wpartial_cap;
+        out[10] = 0;      // a column sum of one row chunk writes its output directly: no scratch
+        for (int w = 0; w < BCS_COUNT; ++w) {
+            int r, c;
+            bott_colsum_shape(m, rows, w, &r, &c);
+            const long long v = (long long)uad_colsum_scratch_floats(r, c);
+            if (v > c && v > out[10]) out[10] = v;
+        }
+        out[11] = (long long)m->colscratch_cap;
         return UAD_OK;
     }
     if (side < 0 || side > 1 || layer < (side == 0 ? 1 : 0) || layer >= (int)(side == 0 ? m->enc.size() : m->dec.size()))

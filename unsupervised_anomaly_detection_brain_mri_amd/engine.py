@@ -979,14 +979,16 @@ class Engine(_EvalOps):
         return torch.as_tensor(_DevArray(ptr.value, cnt.value), device=self.device)
 
     PLAN_FIELDS = {'FD': ('path', 'splits', 'inkernel', 'colblock', 'tiles', 'x6', 'fused_final', '_', 'need', 'cap', 'cp_need', 'cp_cap'),
-                   'W': ('kernel', 'splits', 'short_last', 'csblocks', 'units', 'x6', '_', 'units_per_split', 'need', 'cap', '_', 'cp_cap')}
+                   'W': ('kernel', 'splits', 'short_last', 'csblocks', 'units', 'x6', '_', 'units_per_split', 'need', 'cap', '_', 'cp_cap'),
+                   'B': ('fused', 'wgs', 'fused_wgrad', 'kgroups', 'lds_fwd', 'lds_bwd', 'wgrad_chunks', 'wgrad_last_rows', 'need', 'cap', 'cs_need', 'cs_cap')}
 
     def debug_plan(self, side, layer, kind, n):
-        """tests: what the handle would launch for encoder ('enc') / decoder ('dec') block `layer`, kind 'F' | 'D' | 'W', at batch n in the current math
-        mode (include/uad_hip.h: uad_debug_plan; nothing is launched).  Returns a dict keyed by PLAN_FIELDS."""
+        """tests: what the handle would launch for encoder ('enc') / decoder ('dec') block `layer`, kind 'F' | 'D' | 'W', or for the dense bottleneck
+        ('bott', 0, 'B'; AE / VAE / ceVAE), at batch n in the current math mode (include/uad_hip.h: uad_debug_plan; nothing is launched).  Returns a dict
+        keyed by PLAN_FIELDS."""
         out = (C.c_longlong * 12)()
-        _lib.check(self.lib.uad_debug_plan(self.handle, {'enc': 0, 'dec': 1}[side], int(layer), ord(kind), int(n), out))
-        return {k: int(v) for k, v in zip(self.PLAN_FIELDS['W' if kind == 'W' else 'FD'], out) if k != '_'}
+        _lib.check(self.lib.uad_debug_plan(self.handle, {'enc': 0, 'dec': 1, 'bott': 2}[side], int(layer), ord(kind), int(n), out))
+        return {k: int(v) for k, v in zip(self.PLAN_FIELDS[kind if kind in 'WB' else 'FD'], out) if k != '_'}
 
     def set_math(self, math):
         """'f32' (exact fp32 MFMA), 'bf16x3' (split-bf16 on the bf16 matrix cores, ~2^-17 relative product error) or 'bf16x6' (three bf16 planes per
