@@ -1,77 +1,15 @@
 // Host emulation of uad_cc_props and uad_crop2d (tests/test_crops_kernels_host.py): the kernel source of csrc/uad_crops.hip is compiled for the
-// CPU behind the shim below.  Workgroups run one after the other; the threads of a workgroup are real threads around a std::barrier (the
-// props kernels synchronise around their LDS scans and tables), the atomics are the compiler's; the LDS struct (`__shared__` = a static here)
-// is poisoned before every workgroup, the workspace before the call.  Outputs sit between guard words that must come back untouched.
-// Driven by the library's own launch geometry and workspace layout (props_tiles / props_rank_offset / props_workspace_bytes, crop_blocks /
-// crop_quads_per_row / crop_vec4).
+// CPU behind the shim of hip_host_emu.h.  Workgroups run one after the other; the threads of a workgroup are real threads around a
+// std::barrier (the props kernels synchronise around their LDS scans and tables), the atomics are the compiler's; the LDS struct
+// (`__shared__` = a static here) is poisoned before every workgroup, the workspace before the call.  Outputs sit between guard words that
+// must come back untouched.  Driven by the library's own launch geometry and workspace layout (props_tiles / props_rank_offset /
+// props_workspace_bytes, crop_blocks / crop_quads_per_row / crop_vec4).
 //   crops_emu props labels.i32 D H W max_components props.i64 count.i32      (props.i64 holds min(count, max_components) rows)
 //   crops_emu crop in.f32 n_in h w origins.i32 k ch cw out.f32
-#include <barrier>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-struct dim3 {
-    unsigned x, y, z;
-    dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {}
-};
-struct alignas(16) uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
-thread_local dim3 threadIdx, blockIdx;
-dim3 blockDim, gridDim;
-std::barrier<>* block_barrier = nullptr;
-static void __syncthreads() { block_barrier->arrive_and_wait(); }
-static inline int atomicAdd(int* p, int v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-static inline int atomicCAS(int* p, int expected, int desired) {
-    __atomic_compare_exchange_n(p, &expected, desired, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
-    return expected;                                              // the old value, as the device function returns it
-}
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-#define __restrict__
-#define UAD_CROPS_HOST_EMULATION
+#include "hip_host_emu.h"
 #include "../../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_crops.hip"
 
-// LDS does not survive a workgroup and holds nothing known at its start
 static void poison_lds() { memset(&pr_lds, 0x7f, sizeof(pr_lds)); }
-
-template <class F>
-static void launch_threads(dim3 g, dim3 b, F kernel) {
-    gridDim = g; blockDim = b;
-    std::barrier<> bar(b.x);
-    block_barrier = &bar;
-    for (unsigned by = 0; by < g.y; ++by)
-        for (unsigned bx = 0; bx < g.x; ++bx) {
-            poison_lds();
-            std::vector<std::thread> threads;
-            for (unsigned tx = 0; tx < b.x; ++tx)
-                threads.emplace_back([=] { blockIdx = dim3(bx, by); threadIdx = dim3(tx); kernel(); });
-            for (auto& t : threads) t.join();
-        }
-}
-
-template <class T>
-static bool read_all(const char* path, std::vector<T>& v) {
-    FILE* f = fopen(path, "rb");
-    const bool ok = f && fread(v.data(), sizeof(T), v.size(), f) == v.size();
-    if (f) fclose(f);
-    return ok;
-}
-
-template <class T>
-static bool write_all(const char* path, const T* p, size_t count) {
-    FILE* f = fopen(path, "wb");
-    const bool ok = f && fwrite(p, sizeof(T), count, f) == count;
-    if (f) fclose(f);
-    return ok;
-}
 
 static int run_props(char** a) {
     const int D = atoi(a[1]), H = atoi(a[2]), W = atoi(a[3]), max_components = atoi(a[4]);
@@ -79,10 +17,10 @@ static int run_props(char** a) {
     const long long total = (long long)D * H * W;
     std::vector<int> labels_v(total);
     if (!read_all(a[0], labels_v)) return 2;
-    const long long guard_word = 0x5a5a5a5a5a5a5a5aLL;
-    const size_t rows = (size_t)max_components * PR_COLS, guard = 16;
-    std::vector<long long> raw(rows + 2 * guard, guard_word);
-    long long* props = raw.data() + guard;
+    constexpr long long guard_word = 0x5a5a5a5a5a5a5a5aLL;
+    const size_t rows = (size_t)max_components * PR_COLS;
+    Guarded<long long, guard_word> guarded(rows);
+    long long* props = guarded.p;
     // the workspace holds anything at the start of the call, and the call may not write outside what uad_cc_props_workspace reports
     const size_t ws_bytes = props_workspace_bytes(total);
     std::vector<unsigned char> ws_raw(ws_bytes + 128, 0x7f);
@@ -95,12 +33,11 @@ static int run_props(char** a) {
     int* rank = reinterpret_cast<int*>(ws + props_rank_offset(total));
     const int tiles = (int)props_tiles(total);
     // the four launches of uad_cc_props
-    launch_threads(dim3(tiles), dim3(PR_THREADS), [&] { props_count_kernel(labels, total, tile_count); });
-    launch_threads(dim3(1), dim3(PR_THREADS), [&] { props_scan_kernel(tile_count, tiles, n_components); });
-    launch_threads(dim3(tiles), dim3(PR_THREADS), [&] { props_rank_kernel(labels, total, (const int*)tile_count, rank, props, max_components); });
-    launch_threads(dim3(tiles), dim3(PR_THREADS), [&] { props_accumulate_kernel(labels, total, H, W, (const int*)rank, props, max_components); });
-    for (size_t i = 0; i < guard; ++i)
-        if (raw[i] != guard_word || raw[guard + rows + i] != guard_word) return 4;
+    launch_threads(dim3(tiles), dim3(PR_THREADS), [&] { props_count_kernel(labels, total, tile_count); }, poison_lds);
+    launch_threads(dim3(1), dim3(PR_THREADS), [&] { props_scan_kernel(tile_count, tiles, n_components); }, poison_lds);
+    launch_threads(dim3(tiles), dim3(PR_THREADS), [&] { props_rank_kernel(labels, total, (const int*)tile_count, rank, props, max_components); }, poison_lds);
+    launch_threads(dim3(tiles), dim3(PR_THREADS), [&] { props_accumulate_kernel(labels, total, H, W, (const int*)rank, props, max_components); }, poison_lds);
+    if (!guarded.intact()) return 4;
     for (size_t i = 0; i < ws_head; ++i)
         if (ws_raw[i] != 0x7f) return 4;
     for (size_t i = ws_head + ws_bytes; i < ws_raw.size(); ++i)
@@ -122,20 +59,15 @@ static int run_crop(char** a) {
     for (int j = 0; j < k; ++j)                                     // what engine.crop validates on the host
         if (origins[3 * j] < 0 || origins[3 * j] >= n_in || origins[3 * j + 1] < 0 || origins[3 * j + 1] + ch > h || origins[3 * j + 2] < 0 || origins[3 * j + 2] + cw > w)
             return 1;
-    const size_t count = (size_t)k * ch * cw, guard = 64;
-    const uint32_t guard_word = 0xc4424000u;                       // -777.0f
-    uint32_t* raw = static_cast<uint32_t*>(std::aligned_alloc(16, ((count + 2 * guard) * sizeof(uint32_t) + 15) / 16 * 16));
-    for (size_t i = 0; i < count + 2 * guard; ++i) raw[i] = guard_word;
-    uint32_t* out = raw + guard;
+    const size_t count = (size_t)k * ch * cw;
+    Guarded<uint32_t, 0xc4424000u> guarded(count);                 // -777.0f
+    uint32_t* out = guarded.p;
     const uint32_t* inp = in.data();
     const int* op = origins.data();
     // the launch of uad_crop2d
-    launch_threads(dim3((unsigned)crop_blocks(ch, cw), (unsigned)k), dim3(CR_THREADS), [&] { crop_kernel(inp, h, w, op, ch, cw, crop_quads_per_row(cw), crop_vec4(cw, out), out); });
-    for (size_t i = 0; i < guard; ++i)
-        if (raw[i] != guard_word || raw[guard + count + i] != guard_word) return 4;
-    const bool ok = write_all(a[8], out, count);
-    std::free(raw);
-    return ok ? 0 : 3;
+    launch_threads(dim3((unsigned)crop_blocks(ch, cw), (unsigned)k), dim3(CR_THREADS), [&] { crop_kernel(inp, h, w, op, ch, cw, crop_quads_per_row(cw), crop_vec4(cw, out), out); }, poison_lds);
+    if (!guarded.intact()) return 4;
+    return write_all(a[8], out, count) ? 0 : 3;
 }
 
 int main(int argc, char** argv) {

@@ -1,5 +1,5 @@
 // Host emulation of uad_histogram_by_class (tests/test_histograms_kernels_host.py): the kernel source of csrc/uad_hist.hip is compiled for
-// the CPU (with -ffp-contract=off, as the device build) behind the shim below.  Workgroups run one after the other; the threads of a
+// the CPU (with -ffp-contract=off, as the device build) behind the shim of hip_host_emu.h.  Workgroups run one after the other; the threads of a
 // workgroup are real threads around a std::barrier (the tree reduction synchronises nine times per tile) and live for the whole launch; the
 // LDS struct (`__shared__` = a static here) is poisoned before every workgroup, the workspace of partials before the launch.  Driven by the
 // library's own launch geometry (hc_tiles / hc_grid / hc_lab_vec); max_blocks > 0 caps the grid below the library's, which must not change a
@@ -7,73 +7,10 @@
 // ids by that many BYTES, so that the guarded head / tail chunks and the byte loads of the ids run.
 //   hist_emu in.f32 lab.u8 n n_classes edges.f32|- bins centre.f64|- moments in_off lab_off max_blocks out.bin
 // out.bin: counts int64 [n_classes * bins], class_count int64 [n_classes], sums fp64 [n_classes] (the last two only with moments = 1).
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-struct dim3 {
-    unsigned x, y, z;
-    dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {}
-};
-struct alignas(16) float4 { float x, y, z, w; };
-thread_local dim3 threadIdx, blockIdx;
-dim3 blockDim, gridDim;
-std::barrier<>* block_barrier = nullptr;
-static void __syncthreads() { block_barrier->arrive_and_wait(); }
-static unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-static unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-#define __restrict__
-#define UAD_HIST_HOST_EMULATION
+#include "hip_host_emu.h"
 #include "../../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_hist.hip"
 
-template <class F>
-static void launch_threads(dim3 g, dim3 b, F kernel) {
-    gridDim = g; blockDim = b;
-    std::barrier<> bar(b.x);
-    block_barrier = &bar;
-    std::vector<std::thread> threads;
-    for (unsigned tx = 0; tx < b.x; ++tx)
-        threads.emplace_back([=, &bar] {
-            threadIdx = dim3(tx);
-            for (unsigned bx = 0; bx < g.x; ++bx) {
-                if (tx == 0) memset(&hc_lds, 0xff, sizeof(hc_lds));      // LDS holds nothing known at a workgroup's start
-                bar.arrive_and_wait();
-                blockIdx = dim3(bx);
-                kernel();
-                bar.arrive_and_wait();
-            }
-        });
-    for (auto& t : threads) t.join();
-}
-
-template <class T>
-static bool read_all(const char* path, T* p, size_t count) {
-    FILE* f = fopen(path, "rb");
-    const bool ok = f && fread(p, sizeof(T), count, f) == count;
-    if (f) fclose(f);
-    return ok;
-}
-
-// a 16-byte aligned allocation of count + off elements; the array starts off elements in
-template <class T>
-struct Shifted {
-    void* raw;
-    T* p;
-    Shifted(size_t count, size_t off) {
-        raw = std::aligned_alloc(16, ((count + off) * sizeof(T) + 31) / 16 * 16);
-        p = static_cast<T*>(raw) + off;
-    }
-    ~Shifted() { std::free(raw); }
-};
+static void poison_lds() { memset(&hc_lds, 0xff, sizeof(hc_lds)); }
 
 int main(int argc, char** argv) {
     if (argc != 13) return 1;
@@ -106,9 +43,9 @@ int main(int argc, char** argv) {
     HcPartial* pp = moments ? partials.data() : nullptr;
     const int lab_vec = hc_lab_vec(ip, lp);
     launch_threads(dim3(grid), dim3(HC_THREADS),
-                   [&] { hist_class_kernel(ip, lp, (unsigned long long)n, n_classes, ep, bins, cp, counts.data(), pp, tiles, lab_vec); });
+                   [&] { hist_class_kernel(ip, lp, (unsigned long long)n, n_classes, ep, bins, cp, counts.data(), pp, tiles, lab_vec); }, poison_lds);
     if (moments)
-        launch_threads(dim3(1), dim3(HC_THREADS), [&] { hist_class_finish_kernel(pp, tiles, n_classes, class_count.data(), sums.data()); });
+        launch_threads(dim3(1), dim3(HC_THREADS), [&] { hist_class_finish_kernel(pp, tiles, n_classes, class_count.data(), sums.data()); }, poison_lds);
 
     FILE* f = fopen(argv[12], "wb");
     if (!f) return 3;

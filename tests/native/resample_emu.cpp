@@ -1,60 +1,15 @@
 // Host emulation of the three kernels of csrc/uad_resample.hip (tests/test_resample_kernels_host.py): the kernel source itself is compiled for
-// the CPU behind a shim -- blocks run one after the other; the threads of a block are a plain loop where the kernel has no barrier and real
-// threads around a std::barrier where it has one (zoom_rows_kernel) -- and driven by the same launch geometry as uad_zoom_spline3.
+// the CPU behind the shim of hip_host_emu.h -- the threads of a block are a plain loop where the kernel has no barrier and real threads around
+// a std::barrier where it has one (zoom_rows_kernel) -- and driven by the same launch geometry as uad_zoom_spline3.
 //   resample_emu in.f32 n h w H W boundary out_kind out.bin
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <thread>
-#include <vector>
-
-struct dim3 {
-    unsigned x, y, z;
-    dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {}
-};
-thread_local dim3 threadIdx, blockIdx;
-dim3 blockDim, gridDim;
-std::barrier<>* block_barrier = nullptr;
-static void __syncthreads() { block_barrier->arrive_and_wait(); }
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-#define __restrict__
-#define UAD_RESAMPLE_HOST_EMULATION
+#include "hip_host_emu.h"
 #include "../../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_resample.hip"
-
-template <class F>
-static void launch_loop(dim3 g, dim3 b, F kernel) {
-    gridDim = g; blockDim = b;
-    for (unsigned bz = 0; bz < g.z; ++bz)
-        for (unsigned by = 0; by < g.y; ++by)
-            for (unsigned bx = 0; bx < g.x; ++bx)
-                for (unsigned ty = 0; ty < b.y; ++ty)
-                    for (unsigned tx = 0; tx < b.x; ++tx) { blockIdx = dim3(bx, by, bz); threadIdx = dim3(tx, ty, 0); kernel(); }
-}
-
-template <class F>
-static void launch_threads(dim3 g, dim3 b, F kernel) {
-    gridDim = g; blockDim = b;
-    std::barrier<> bar(b.x);
-    block_barrier = &bar;
-    for (unsigned bx = 0; bx < g.x; ++bx) {
-        std::vector<std::thread> threads;
-        for (unsigned tx = 0; tx < b.x; ++tx) threads.emplace_back([=] { blockIdx = dim3(bx, 0, 0); threadIdx = dim3(tx, 0, 0); kernel(); });
-        for (auto& t : threads) t.join();
-    }
-}
 
 int main(int argc, char** argv) {
     if (argc != 10) return 1;
     const int n = atoi(argv[2]), h = atoi(argv[3]), w = atoi(argv[4]), H = atoi(argv[5]), W = atoi(argv[6]), boundary = atoi(argv[7]), out_kind = atoi(argv[8]);
     std::vector<float> in((size_t)n * h * w);
-    FILE* f = fopen(argv[1], "rb");
-    if (!f || fread(in.data(), 4, in.size(), f) != in.size()) return 2;
-    fclose(f);
+    if (!read_all(argv[1], in.data(), in.size())) return 2;
     std::vector<int> out((size_t)n * H * W);                    // 4-byte elements either way
     // the launch sequence of uad_zoom_spline3
     const int pad = zoom_pad(boundary), hp = h + 2 * pad, wp = w + 2 * pad;
@@ -70,8 +25,5 @@ int main(int argc, char** argv) {
     launch_loop(dim3((unsigned)((cols + 255) / 256)), dim3(256), [&] { zoom_cols_kernel(src, n, h, w, pad, hp, wp, z, zny, c); });
     launch_threads(dim3((unsigned)((rows + ZOOM_TILE - 1) / ZOOM_TILE)), dim3(ZOOM_TILE), [&] { zoom_rows_kernel(c, rows, wp, z, znx); });
     launch_loop(dim3((W + 63) / 64, (H + 3) / 4, n < 2 ? n : 2), dim3(64, 4), [&] { zoom_interp_kernel(c, n, pad, hp, wp, H, W, zy, zx, out_kind, dst); });
-    f = fopen(argv[9], "wb");
-    if (!f || fwrite(out.data(), 4, out.size(), f) != out.size()) return 3;
-    fclose(f);
-    return 0;
+    return write_all(argv[9], out.data(), out.size()) ? 0 : 3;
 }

@@ -1,76 +1,18 @@
 // Host emulation of uad_resize2d and uad_mask_by_label (tests/test_resize_kernels_host.py): the kernel source of csrc/uad_resize.hip is
-// compiled for the CPU (with -ffp-contract=off, as the device build) behind the shim below.  Workgroups run one after the other; the
+// compiled for the CPU (with -ffp-contract=off, as the device build) behind the shim of hip_host_emu.h.  Workgroups run one after the other; the
 // threads of a workgroup are real threads around a std::barrier, because both kernels synchronise once after filling their LDS tables;
 // the tables (`__shared__` = a static here) are poisoned before every workgroup.
 // Driven by the library's own launch geometry (resize_grid / resize_block / resize_vec4, mask_label_grid / mask_label_vec4).
 //   resize_emu resize in.f32 n_in h w idx.i32|- n H W mode out.f32
 //   resize_emu mask vol.f32 labels.u8 n lut.u8 lesion_label want_lesion in_place out.f32 lesion.f32
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-
-struct dim3 {
-    unsigned x, y, z;
-    dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {}
-};
-struct alignas(16) float4 { float x, y, z, w; };
-struct alignas(16) int4 { int x, y, z, w; };
-struct alignas(4) uchar4 { unsigned char x, y, z, w; };
-static inline float4 make_float4(float a, float b, float c, float d) { return float4{a, b, c, d}; }
-thread_local dim3 threadIdx, blockIdx;
-dim3 blockDim, gridDim;
-std::barrier<>* block_barrier = nullptr;
-static void __syncthreads() { block_barrier->arrive_and_wait(); }
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __shared__ static
-#define __restrict__
-#define UAD_RESIZE_HOST_EMULATION
+#include "hip_host_emu.h"
 #include "../../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_resize.hip"
 
-// LDS does not survive a workgroup and holds nothing known at its start: every table is filled with 0x7f bytes before each workgroup (as an
-// index that is 2139062143, as a float a NaN), so that a kernel reading an entry its own workgroup never wrote goes visibly wrong
+// every table is filled with 0x7f bytes before each workgroup (as an index that is 2139062143, as a float a NaN), so that a kernel reading
+// an entry its own workgroup never wrote goes visibly wrong
 static void poison_lds() {
     memset(&rs_lds, 0x7f, sizeof(rs_lds));
     memset(ml_lut, 0x7f, sizeof(ml_lut));
-}
-
-template <class F>
-static void launch_threads(dim3 g, dim3 b, F kernel) {
-    gridDim = g; blockDim = b;
-    std::barrier<> bar(b.x);
-    block_barrier = &bar;
-    for (unsigned bz = 0; bz < g.z; ++bz)
-        for (unsigned by = 0; by < g.y; ++by)
-            for (unsigned bx = 0; bx < g.x; ++bx) {
-                poison_lds();
-                std::vector<std::thread> threads;
-                for (unsigned tx = 0; tx < b.x; ++tx)
-                    threads.emplace_back([=] { blockIdx = dim3(bx, by, bz); threadIdx = dim3(tx); kernel(); });
-                for (auto& t : threads) t.join();
-            }
-}
-
-template <class T>
-static bool read_all(const char* path, std::vector<T>& v) {
-    FILE* f = fopen(path, "rb");
-    const bool ok = f && fread(v.data(), sizeof(T), v.size(), f) == v.size();
-    if (f) fclose(f);
-    return ok;
-}
-
-template <class T>
-static bool write_all(const char* path, const T* p, size_t count) {
-    FILE* f = fopen(path, "wb");
-    const bool ok = f && fwrite(p, sizeof(T), count, f) == count;
-    if (f) fclose(f);
-    return ok;
 }
 
 static int run_resize(char** a) {
@@ -88,19 +30,15 @@ static int run_resize(char** a) {
         return 1;
     }
     // the output sits between two guard rows that must come back untouched
-    const size_t count = (size_t)n * H * W, guard = 64;
-    float* raw = static_cast<float*>(std::aligned_alloc(16, ((count + 2 * guard) * sizeof(float) + 15) / 16 * 16));
-    for (size_t i = 0; i < count + 2 * guard; ++i) raw[i] = -777.0f;
-    float* out = raw + guard;
+    const size_t count = (size_t)n * H * W;
+    Guarded<float, -777.0f> guarded(count);
+    float* out = guarded.p;
     const int* ip = idx.empty() ? nullptr : idx.data();
     const float* inp = in.data();
     // the launch of uad_resize2d
-    launch_threads(resize_grid(n, H, W), resize_block(), [&] { resize_kernel(inp, h, w, ip, H, W, mode, resize_vec4(W, out), out); });
-    for (size_t i = 0; i < guard; ++i)
-        if (raw[i] != -777.0f || raw[guard + count + i] != -777.0f) return 4;
-    const bool ok = write_all(a[9], out, count);
-    std::free(raw);
-    return ok ? 0 : 3;
+    launch_threads(resize_grid(n, H, W), resize_block(), [&] { resize_kernel(inp, h, w, ip, H, W, mode, resize_vec4(W, out), out); }, poison_lds);
+    if (!guarded.intact()) return 4;
+    return write_all(a[9], out, count) ? 0 : 3;
 }
 
 static int run_mask(char** a) {
@@ -115,7 +53,7 @@ static int run_mask(char** a) {
     const float* v = vol.data();
     const unsigned char *lb = labels.data(), *lt = lut.data();
     // the launch of uad_mask_by_label
-    launch_threads(mask_label_grid(n), dim3(ML_THREADS), [&] { mask_label_kernel(v, lb, n, lt, out, les, lesion_label, mask_label_vec4(v, lb, out, les)); });
+    launch_threads(mask_label_grid(n), dim3(ML_THREADS), [&] { mask_label_kernel(v, lb, n, lt, out, les, lesion_label, mask_label_vec4(v, lb, out, les)); }, poison_lds);
     if (!write_all(a[7], out, n)) return 3;
     if (want_lesion && !write_all(a[8], les, n)) return 3;
     return 0;

@@ -11,16 +11,12 @@ import numpy as np
 import pytest
 
 from tests import crops_cases as cc
-from tests.test_resample_kernels_host import _clangxx
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.emu_build import build_emu
 
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('crops_emu') / 'crops_emu')
-    subprocess.run([_clangxx(), '-std=c++20', '-O1', '-x', 'c++', '-Wno-unknown-pragmas', os.path.join(ROOT, 'tests', 'native', 'crops_emu.cpp'), '-o', exe, '-lpthread'],
-                   check=True)
+    exe = build_emu(tmp_path_factory, 'crops_emu', 'uad_crops.hip')
     d = os.path.dirname(exe)
 
     def props(labels, max_components):

@@ -10,16 +10,12 @@ import numpy as np
 import pytest
 
 from tests import flow_cases as fc
-from tests.test_resample_kernels_host import _clangxx
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.emu_build import build_emu
 
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('flow_emu') / 'flow_emu')
-    subprocess.run([_clangxx(), '-std=c++20', '-O1', '-ffp-contract=off', '-x', 'c++', '-Wno-unknown-pragmas', os.path.join(ROOT, 'tests', 'native', 'flow_emu.cpp'),
-                    '-o', exe, '-lpthread'], check=True)
+    exe = build_emu(tmp_path_factory, 'flow_emu', 'uad_flow.hip')
 
     def run(vol, spacing, iterations, time_step=fc.TIME_STEP):
         d = os.path.dirname(exe)

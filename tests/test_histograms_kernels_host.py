@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests import hist_cases as hc
-from tests.test_resample_kernels_host import _clangxx
+from tests.emu_build import build_emu
 from unsupervised_anomaly_detection_brain_mri_amd.utils.order_stats import edges_to_float32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,9 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('hist_emu') / 'hist_emu')
-    subprocess.run([_clangxx(), '-std=c++20', '-O1', '-ffp-contract=off', '-x', 'c++', '-Wno-unknown-pragmas', os.path.join(ROOT, 'tests', 'native', 'hist_emu.cpp'),
-                    '-o', exe, '-lpthread'], check=True)
+    exe = build_emu(tmp_path_factory, 'hist_emu', 'uad_hist.hip')
     d = os.path.dirname(exe)
     f = lambda name: os.path.join(d, name)
 

@@ -12,17 +12,13 @@ import numpy as np
 import pytest
 
 from tests import render_cases as rc
-from tests.test_resample_kernels_host import _clangxx
+from tests.emu_build import build_emu
 from unsupervised_anomaly_detection_brain_mri_amd.utils import render
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('render_emu') / 'render_emu')
-    subprocess.run([_clangxx(), '-std=c++20', '-O1', '-ffp-contract=off', '-x', 'c++', '-Wno-unknown-pragmas', os.path.join(ROOT, 'tests', 'native', 'render_emu.cpp'),
-                    '-o', exe, '-lpthread'], check=True)
+    exe = build_emu(tmp_path_factory, 'render_emu', 'uad_render.hip')
     d = os.path.dirname(exe)
     f = lambda name: os.path.join(d, name)
 

@@ -4,31 +4,20 @@ with the launch geometry of uad_zoom_spline3.  Same reference and bars as tests/
 fp32 output within 1.2e-7 (twice the half-ulp of the final rounding for |v| < 2); int32 output equal wherever scipy's unrounded value is not
 within 1e-9 of a half-integer (2-sample lines do produce such ties; the GPU test's inputs have none)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 import scipy.ndimage
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.emu_build import build_emu
+
 CASES = [(217, 181, 128, 128), (128, 128, 217, 181), (80, 80, 64, 64), (64, 64, 80, 80), (100, 60, 50, 90), (5, 40, 8, 64), (2, 3, 5, 4), (30, 150, 31, 70)]
-
-
-def _clangxx():
-    hipcc = os.environ.get('HIPCC') or shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
-    for c in (os.path.join(os.path.dirname(os.path.realpath(hipcc)), '..', 'lib', 'llvm', 'bin', 'clang++'), '/opt/rocm/lib/llvm/bin/clang++',
-              shutil.which('clang++'), shutil.which('g++')):
-        if c and os.path.exists(c):
-            return c
-    raise RuntimeError('no host C++ compiler found (the HIP toolchain ships clang++)')
 
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('resample_emu') / 'resample_emu')
-    subprocess.run([_clangxx(), '-std=c++20', '-O1', '-x', 'c++', '-Wno-unknown-pragmas', os.path.join(ROOT, 'tests', 'native', 'resample_emu.cpp'), '-o', exe,
-                    '-lpthread'], check=True)
+    exe = build_emu(tmp_path_factory, 'resample_emu', 'uad_resample.hip')
 
     def run(a, H, W, mode, integer):
         n, h, w = a.shape

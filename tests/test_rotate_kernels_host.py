@@ -11,17 +11,14 @@ import pytest
 import scipy.ndimage
 
 from tests import rotate_cases as rc
-from tests.test_resample_kernels_host import _clangxx
+from tests.emu_build import build_emu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = rc.SHAPES + [(2, 9)]
 
 
 @pytest.fixture(scope='module')
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('affine_emu') / 'affine_emu')
-    subprocess.run([_clangxx(), '-std=c++20', '-O1', '-x', 'c++', '-Wno-unknown-pragmas', os.path.join(ROOT, 'tests', 'native', 'affine_emu.cpp'), '-o', exe,
-                    '-lpthread'], check=True)
+    exe = build_emu(tmp_path_factory, 'affine_emu', 'uad_resample.hip')
 
     def run(a, xf, out_hw, mode, integer):
         n, h, w = a.shape

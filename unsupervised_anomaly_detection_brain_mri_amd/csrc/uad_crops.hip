@@ -20,12 +20,12 @@
 // crop_kernel, one launch: a thread owns four consecutive pixels of one window row (grid = quads of a window x k); lanes walk a row in
 // ascending address order; 16-byte stores where the crop width is a multiple of four and `out` is 16-byte aligned, the loads are single words
 // because `left` is arbitrary.  Words are moved as uint32: every bit pattern survives.
-// tests/native/crops_emu.cpp compiles the kernels of this file for the HOST (UAD_CROPS_HOST_EMULATION: a shim supplies threadIdx & co. and the
+// tests/native/crops_emu.cpp compiles the kernels of this file for the HOST (UAD_HOST_EMULATION: hip_host_emu.h supplies threadIdx & co. and the
 // atomics, the launch layer at the end of the file is left out).
 #include <cstddef>
 #include <cstdint>
 
-#ifndef UAD_CROPS_HOST_EMULATION
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)   // a compile that is not a HIP one is a host emulation too
 #include "uad_kernels.h"
 #endif
 #include "../../include/uad_hip.h"
@@ -188,8 +188,7 @@ inline int crop_vec4(int cw, const void* out) { return cw % CR_PX == 0 && (uintp
 
 }  // namespace
 
-#ifndef UAD_CROPS_HOST_EMULATION
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 #define fail uad_fail
 
 extern "C" {
@@ -237,4 +236,4 @@ int uad_crop2d(const float* in, int n_in, int h, int w, const int* origins, int 
 }
 
 }  // extern "C"
-#endif  // UAD_CROPS_HOST_EMULATION
+#endif  // UAD_HOST_EMULATION

@@ -12,7 +12,6 @@
 #include "uad_kernels.h"
 #include "../../include/uad_hip.h"
 
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
 #define fail uad_fail
 
 #define EV_TRY(expr)                                                                              \

@@ -12,12 +12,12 @@
 //   Halo cells are loaded with CLAMPED global indices, which is the boundary rule; the loads of plane z + 2 are issued into registers before
 //   the arithmetic of plane z and stored to LDS after it.  A lane is an x position: the 32 lanes of a half-wave read 256 contiguous bytes
 //   of one LDS row whatever the tap offset, which covers the 64 banks once (ds_read_b64: no conflict).
-// tests/native/flow_emu.cpp compiles the kernels of this file for the HOST (UAD_FLOW_HOST_EMULATION: a shim supplies threadIdx & co., the
+// tests/native/flow_emu.cpp compiles the kernels of this file for the HOST (UAD_HOST_EMULATION: hip_host_emu.h supplies threadIdx & co., the
 // launch layer at the end of the file is left out).
 #include <cmath>
 #include <cstddef>
 
-#ifndef UAD_FLOW_HOST_EMULATION
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)   // a compile that is not a HIP one is a host emulation too
 #include "uad_kernels.h"
 #endif
 #include "../../include/uad_hip.h"
@@ -127,8 +127,7 @@ inline dim3 flow_block() { return dim3(FLOW_TX, FLOW_TY); }
 
 }  // namespace
 
-#ifndef UAD_FLOW_HOST_EMULATION
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 #define fail uad_fail
 
 #define FLOW_TRY(expr)                                                                            \
@@ -192,4 +191,4 @@ int uad_curvature_flow(const void* in, int in_is_f32, int nz, int ny, int nx, co
 }
 
 }  // extern "C"
-#endif  // UAD_FLOW_HOST_EMULATION
+#endif  // UAD_HOST_EMULATION

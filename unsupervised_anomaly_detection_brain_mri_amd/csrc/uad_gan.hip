@@ -25,7 +25,6 @@
 #include "uad_allreduce.h"
 #include "uad_kernels.h"
 
-int uad_fail(int code, const char* fmt, ...);
 #define fail uad_fail
 
 namespace {

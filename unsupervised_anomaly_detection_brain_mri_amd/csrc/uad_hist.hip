@@ -9,13 +9,13 @@
 // No floating-point atomic anywhere: the sums are bit-identical from run to run and do not depend on the grid or on what else runs.
 // The longest chain of dependent fp64 additions is HC_RUN + 8 + ceil(tiles / 256) + 8 <= UAD_HISTOGRAM_SUM_CHAIN for every n the entry accepts.
 // Bytes: one launch reads 4 B (value) + 1 B (class id) per voxel and writes 64 B per tile of 8192 (0.008 B per voxel).
-// tests/native/hist_emu.cpp compiles the kernels of this file for the HOST (UAD_HIST_HOST_EMULATION: a shim supplies threadIdx & co., the
+// tests/native/hist_emu.cpp compiles the kernels of this file for the HOST (UAD_HOST_EMULATION: hip_host_emu.h supplies threadIdx & co., the
 // launch layer at the end of the file is left out).
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 
-#ifndef UAD_HIST_HOST_EMULATION
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)   // a compile that is not a HIP one is a host emulation too
 #include "uad_kernels.h"
 #endif
 #include "../../include/uad_hip.h"
@@ -190,8 +190,7 @@ inline int hc_lab_vec(const float* in, const uint8_t* labels) {
 
 }  // namespace
 
-#ifndef UAD_HIST_HOST_EMULATION
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 #define fail uad_fail
 
 #define HC_TRY(expr)                                                                              \
@@ -245,4 +244,4 @@ int uad_histogram_by_class(const float* in, const uint8_t* labels, long long n, 
 }
 
 }  // extern "C"
-#endif  // UAD_HIST_HOST_EMULATION
+#endif  // UAD_HOST_EMULATION

@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// records the message uad_last_error() returns and hands `code` back (uad_model.hip); the entry points' `return fail(...)`
+int uad_fail(int code, const char* fmt, ...);
+
 // One strided-conv relation between a "big" (finer grid) and a "small" image:
 //   big pixel  (S*i - P + ky, S*j - P + kx)  <->  small pixel (i, j),  tap (ky,kx)
 // Weight tensor is always W[tap][cb][cs] (big-side channel first):

@@ -21,7 +21,7 @@
 
 static thread_local std::string g_err;
 
-// records the message uad_last_error() returns; shared with uad_eval.hip
+// records the message uad_last_error() returns; declared in uad_kernels.h for every launch layer
 int uad_fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;

@@ -21,7 +21,7 @@
 //   the two-sweep form above that: the kernel is bound by the exp() there, not by the second read.
 // overlay_kernel: no reduction; the batch is one flat array, a thread owns four pixels: 16-byte loads of image and prediction, one dword of
 //   labels, three dwords of RGB (bytes for the last total % 4 pixels, or everywhere when a pointer is not aligned).
-// tests/native/render_emu.cpp compiles the kernels of this file for the HOST (UAD_RENDER_HOST_EMULATION: a shim supplies threadIdx & co.,
+// tests/native/render_emu.cpp compiles the kernels of this file for the HOST (UAD_HOST_EMULATION: hip_host_emu.h supplies threadIdx & co.,
 // the launch layer at the end of the file is left out).
 #include <cfloat>
 #include <climits>
@@ -29,7 +29,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#ifndef UAD_RENDER_HOST_EMULATION
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)   // a compile that is not a HIP one is a host emulation too
 #include "uad_kernels.h"
 #endif
 #include "../../include/uad_hip.h"
@@ -313,8 +313,7 @@ inline dim3 overlay_grid(long long total) {
 
 }  // namespace
 
-#ifndef UAD_RENDER_HOST_EMULATION
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 #define fail uad_fail
 
 extern "C" {
@@ -368,4 +367,4 @@ int uad_render_overlay(const float* x, const float* pred, const uint8_t* gt, int
 }
 
 }  // extern "C"
-#endif  // UAD_RENDER_HOST_EMULATION
+#endif  // UAD_HOST_EMULATION

@@ -11,21 +11,18 @@
 // All arithmetic is fp64 and written in scipy's order of operations (ni_splines.c, ni_interpolation.c: NI_ZoomShift) without fused
 // multiply-adds, because the integer maps must round as scipy rounds them.  Latency- and bandwidth-shaped work: no matrix cores, no
 // atomics (a slice's bits do not depend on the batch around it), vector stores only.
-// tests/native/resample_emu.cpp compiles the kernels of this file for the HOST (UAD_RESAMPLE_HOST_EMULATION: a shim supplies threadIdx & co.,
+// tests/native/resample_emu.cpp compiles the kernels of this file for the HOST (UAD_HOST_EMULATION: hip_host_emu.h supplies threadIdx & co.,
 // the launch layer at the end of the file is left out), so that their arithmetic is checked against scipy without a GPU.
 #include <cmath>
 
-#ifndef UAD_RESAMPLE_HOST_EMULATION
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)   // a compile that is not a HIP one is a host emulation too
 #include "uad_kernels.h"
 #endif
 #include "../../include/uad_hip.h"
 
 #pragma clang fp contract(off)
 
-#ifndef UAD_RESAMPLE_HOST_EMULATION
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
 #define fail uad_fail
-#endif
 
 #define RS_TRY(expr)                                                                              \
     do {                                                                                          \
@@ -286,7 +283,7 @@ __global__ void __launch_bounds__(256) affine_interp_kernel(const double* __rest
 
 }  // namespace
 
-#ifndef UAD_RESAMPLE_HOST_EMULATION
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 extern "C" {
 
 size_t uad_zoom_spline3_workspace(int n, int h, int w, int boundary) {
@@ -377,4 +374,4 @@ int uad_affine_spline3(const float* in, int n, int h, int w, int H, int W, const
 }
 
 }  // extern "C"
-#endif  // UAD_RESAMPLE_HOST_EMULATION
+#endif  // UAD_HOST_EMULATION

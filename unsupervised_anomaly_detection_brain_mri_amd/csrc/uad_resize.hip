@@ -17,13 +17,13 @@
 //   gather reads slice_idx[blockIdx.z]; no atomics, a slice's bits depend on neither n nor its place in the batch.
 // mask_label_kernel: out = lut256[label] ? vol : 0 and lesion = label == lesion_label in one pass, four elements a thread where the
 //   pointers allow 16-byte accesses.
-// tests/native/resize_emu.cpp compiles the kernels of this file for the HOST (UAD_RESIZE_HOST_EMULATION: a shim supplies threadIdx & co.,
+// tests/native/resize_emu.cpp compiles the kernels of this file for the HOST (UAD_HOST_EMULATION: hip_host_emu.h supplies threadIdx & co.,
 // the launch layer at the end of the file is left out).
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 
-#ifndef UAD_RESIZE_HOST_EMULATION
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)   // a compile that is not a HIP one is a host emulation too
 #include "uad_kernels.h"
 #endif
 #include "../../include/uad_hip.h"
@@ -172,8 +172,7 @@ inline int mask_label_vec4(const void* vol, const void* labels, const void* out,
 
 }  // namespace
 
-#ifndef UAD_RESIZE_HOST_EMULATION
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
+#if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 #define fail uad_fail
 
 extern "C" {
@@ -206,4 +205,4 @@ int uad_mask_by_label(const float* vol, const unsigned char* labels, long long n
 }
 
 }  // extern "C"
-#endif  // UAD_RESIZE_HOST_EMULATION
+#endif  // UAD_HOST_EMULATION

@@ -24,7 +24,6 @@
 
 #pragma clang fp contract(off)
 
-int uad_fail(int code, const char* fmt, ...);   // uad_model.hip
 #define fail uad_fail
 
 #define SEL_TRY(expr)                                                                             \
