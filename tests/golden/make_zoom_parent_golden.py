@@ -18,7 +18,7 @@ SEED, N, CASE = 11, 3, (100, 60, 50, 90)
 
 def main():
     from unsupervised_anomaly_detection_brain_mri_amd import _lib
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     assert os.environ.get('UAD_LIB') and _lib.LIB_PATH == os.environ['UAD_LIB'], 'point UAD_LIB at the parent commit\'s library'
     import ctypes
     import torch  # noqa: F401  (before the library: _lib.load)
@@ -29,7 +29,7 @@ def main():
     h, w, H, W = CASE
     a = np.random.default_rng(SEED).random((N, h, w)).astype(np.float32)
     m = (a * 3).astype(np.int64)
-    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    eng = DeviceOps()
     rec = {'seed': np.int64(SEED), 'input': a}
     for mode in ('constant', 'nearest'):
         rec[f'f32_{mode}'] = eng.zoom(a, (H, W), mode=mode).cpu().numpy()

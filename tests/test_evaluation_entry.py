@@ -31,7 +31,7 @@ class _HostScores:
 
 
 class HostEvalEngine:
-    """The _EvalOps surface of engine.Engine on torch CPU tensors, computed by oracle/scoring.py."""
+    """The device_ops.DeviceOps surface of engine.Engine on torch CPU tensors, computed by oracle/scoring.py."""
     device = torch.device('cpu')
 
     def _dev(self, a):

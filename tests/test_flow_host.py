@@ -177,7 +177,7 @@ def test_bad_arguments_are_refused_before_any_device_work():
 
 
 class _FlowEngine:
-    """A host stand-in with engine._EvalOps.curvature_flow's signature that records its calls (no other op: the rest of the path stays on the host)."""
+    """A host stand-in with device_ops.DeviceOps.curvature_flow's signature that records its calls (no other op: the rest of the path stays on the host)."""
 
     def __init__(self):
         self.calls = []

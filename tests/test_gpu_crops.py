@@ -1,5 +1,5 @@
-"""GPU: the device component measurements (uad_cc_props behind engine._EvalOps.region_props), the window gather (uad_crop2d behind
-engine._EvalOps.crop) and the crop modes of the slice ingestion on them (nifti.volume_to_slices(crops=..., engine=...),
+"""GPU: the device component measurements (uad_cc_props behind device_ops.DeviceOps.region_props), the window gather (uad_crop2d behind
+device_ops.DeviceOps.crop) and the crop modes of the slice ingestion on them (nifti.volume_to_slices(crops=..., engine=...),
 nifti.build_cache).
 
 The reference is always the host statement utils/crops.py (pinned by tests/test_crops_host.py against literal restatements of the reference
@@ -19,15 +19,15 @@ pytestmark = pytest.mark.gpu
 
 try:
     from unsupervised_anomaly_detection_brain_mri_amd import _lib
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.utils import nifti
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

@@ -12,17 +12,17 @@ from oracle import scoring as osc
 pytestmark = pytest.mark.gpu
 
 try:
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.trainers import Metrics
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'scoring_golden.npz'))
 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

@@ -1,4 +1,4 @@
-"""GPU: the device curvature-flow filter (uad_curvature_flow through engine._EvalOps.curvature_flow) and the ingestion on it
+"""GPU: the device curvature-flow filter (uad_curvature_flow through device_ops.DeviceOps.curvature_flow) and the ingestion on it
 (nifti.volume_to_slices(curvature_flow=...), nifti.build_cache).
 
 The reference is always the host statement utils/curvature_flow.py (pinned by tests/test_flow_host.py), never the code under test; volumes
@@ -16,18 +16,18 @@ from tests import flow_cases as fc
 pytestmark = pytest.mark.gpu
 
 try:
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.utils import nifti
     from unsupervised_anomaly_detection_brain_mri_amd.utils.curvature_flow import curvature_flow
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 F32_BAR = 1.2e-7            # tests/test_gpu_resample.py
 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

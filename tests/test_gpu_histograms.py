@@ -20,11 +20,11 @@ pytestmark = pytest.mark.gpu
 
 try:
     from unsupervised_anomaly_detection_brain_mri_amd import _lib
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation, histograms as H
     from unsupervised_anomaly_detection_brain_mri_amd.utils.order_stats import edges_to_float32
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 KIND_BINS = tuple(zip(hc.KINDS, (1024, 1025, 2, 1, 50, 2049)))       # every bin count of hc.BINS; the values on the edges meet the chunk edge
 assert sorted(b for _, b in KIND_BINS) == sorted(hc.BINS)
@@ -32,7 +32,7 @@ assert sorted(b for _, b in KIND_BINS) == sorted(hc.BINS)
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

@@ -14,11 +14,11 @@ from tests.scoring_cases import host_threshold
 pytestmark = pytest.mark.gpu
 
 try:
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.trainers import Metrics
     from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 FULL = np.ones((3, 3, 3), bool)
 SHAPES = [(7, 37, 53), (41, 128, 128), (110, 256, 256)]
@@ -26,7 +26,7 @@ SHAPES = [(7, 37, 53), (41, 128, 128), (110, 256, 256)]
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

@@ -1,5 +1,5 @@
 """GPU: the device renderings of the evaluation sample images (uad_render_minmax_u8 / uad_render_heatmap / uad_render_overlay through
-engine._EvalOps.render_gray / render_heatmap / render_overlay) and options['exportSamples'] on them.
+device_ops.DeviceOps.render_gray / render_heatmap / render_overlay) and options['exportSamples'] on them.
 
 The reference is always the host statement utils/render.py (pinned by tests/test_render_host.py), never the code under test; shapes, inputs
 and references come from tests/render_cases.py, computed once and shared.  Grey, label and overlay images are held to BIT EQUALITY: the
@@ -20,15 +20,15 @@ pytestmark = pytest.mark.gpu
 
 try:
     from unsupervised_anomaly_detection_brain_mri_amd import _lib
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation, png, render
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

@@ -1,4 +1,4 @@
-"""GPU: the device cubic-spline slice resampler (uad_zoom_spline3 through engine._EvalOps.zoom) and the paths built on it
+"""GPU: the device cubic-spline slice resampler (uad_zoom_spline3 through device_ops.DeviceOps.zoom) and the paths built on it
 (Evaluation.collect_patient_volume(engine=...), options['resampleOnDevice'] / ['exportVolumes'], nifti.volume_to_slices(engine=...)).
 
 The reference is always scipy.ndimage.zoom run in fp64 on the fp32-rounded input, never the code under test.
@@ -18,12 +18,12 @@ import torch
 pytestmark = pytest.mark.gpu
 
 try:
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine, zoom_output_hw
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps, zoom_output_hw
     from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation, nifti
     from unsupervised_anomaly_detection_brain_mri_amd.utils.default_config_setup import get_options
     from unsupervised_anomaly_detection_brain_mri_amd.utils.synthetic import SyntheticPatientDataset
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 F32_BAR = 1.2e-7
 TIE_WINDOW = 1e-9
@@ -35,7 +35,7 @@ BATCHES = (1, 7)             # n = 1 and a ragged n (not a multiple of any tile 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

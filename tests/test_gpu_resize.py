@@ -1,5 +1,5 @@
-"""GPU: the device resize op (uad_resize2d through engine._EvalOps.resize), the tissue-class masking (uad_mask_by_label through
-engine._EvalOps.mask_by_label) and the BrainWeb ingestion on them (nifti.volume_to_slices(loader='brainweb', engine=...), nifti.build_cache).
+"""GPU: the device resize op (uad_resize2d through device_ops.DeviceOps.resize), the tissue-class masking (uad_mask_by_label through
+device_ops.DeviceOps.mask_by_label) and the BrainWeb ingestion on them (nifti.volume_to_slices(loader='brainweb', engine=...), nifti.build_cache).
 
 The reference is always the host statement utils/resize.py (pinned by tests/test_resize_host.py) or numpy, never the code under test; shapes,
 inputs and references come from tests/resize_cases.py, computed once and shared.  The kernel performs the host statement's IEEE operations
@@ -19,17 +19,17 @@ pytestmark = pytest.mark.gpu
 
 try:
     from unsupervised_anomaly_detection_brain_mri_amd import _lib
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.utils import nifti
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 F32_BAR = 1.2e-7            # tests/test_gpu_rotate.py
 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

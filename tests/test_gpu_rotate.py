@@ -1,4 +1,4 @@
-"""GPU: the device cubic-spline rotation (uad_affine_spline3 through engine._EvalOps.affine / rotate) and nifti.volume_to_slices' rotation
+"""GPU: the device cubic-spline rotation (uad_affine_spline3 through device_ops.DeviceOps.affine / rotate) and nifti.volume_to_slices' rotation
 augmentation on it.
 
 The reference is always scipy (ndimage.rotate / affine_transform) run in fp64 on the fp32-rounded input, never the code under test; inputs,
@@ -19,17 +19,17 @@ from tests import rotate_cases as rc
 pytestmark = pytest.mark.gpu
 
 try:
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine, rotation_transform
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps, rotation_transform
     from unsupervised_anomaly_detection_brain_mri_amd.utils import nifti
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'zoom_parent_golden.npz')
 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

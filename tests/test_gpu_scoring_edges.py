@@ -25,16 +25,16 @@ from tests import scoring_cases as sc
 pytestmark = pytest.mark.gpu
 
 try:
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.trainers import Metrics
     from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation
 except Exception:
-    Engine = None
+    DeviceOps = None
 
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

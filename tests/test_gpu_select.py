@@ -15,12 +15,12 @@ pytestmark = pytest.mark.gpu
 
 try:
     from unsupervised_anomaly_detection_brain_mri_amd import _lib
-    from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+    from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
     from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation, nifti
     from unsupervised_anomaly_detection_brain_mri_amd.utils.synthetic import SyntheticPatientDataset
     T = _lib.SELECT_TILE
 except Exception:
-    Engine, T = None, 8192
+    DeviceOps, T = None, 8192
 
 SIZES = (1, 2, 3, 63, 64, 65, 255, 256, 257, T - 1, T, T + 1, 2 * T + 1)
 BIG = 4198401
@@ -28,7 +28,7 @@ BIG = 4198401
 
 @pytest.fixture(scope='module')
 def eng():
-    e = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    e = DeviceOps()
     yield e
     e.close()
 

@@ -77,7 +77,7 @@ class HostEvalEngine:
 
 
 class ZoomingHostEngine(HostEvalEngine):
-    """... plus a scipy-backed `zoom` with engine._EvalOps.zoom's signature that records its calls."""
+    """... plus a scipy-backed `zoom` with device_ops.DeviceOps.zoom's signature that records its calls."""
 
     def __init__(self):
         self.zoom_calls = []

@@ -153,7 +153,7 @@ class _HostZoomEngine:
 
 
 class _HostRotateEngine(_HostZoomEngine):
-    """... plus a scipy-backed `rotate` with engine._EvalOps.rotate's signature that records its calls."""
+    """... plus a scipy-backed `rotate` with device_ops.DeviceOps.rotate's signature that records its calls."""
 
     def __init__(self):
         self.calls = []

@@ -94,8 +94,8 @@ def main():
         loader = {'loader': 'brainweb', 'skull_removal': not a.no_skull_removal, 'background_removal': not a.no_background_removal}
     engine = None
     if a.device_resample or a.device_stats:
-        from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
-        engine = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)       # any handle carries the model-independent device ops
+        from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
+        engine = DeviceOps()       # the model-independent device ops: ingestion needs no model
     info = nifti.build_cache(a.cache, patients, partition={'TRAIN': a.train, 'VAL': a.val, 'TEST': a.test}, seed=a.seed, engine=engine, axis=a.axis,
                              slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'rotations': tuple(a.rotations)} if list(a.rotations) != [0] else {}),
                              **({'device_stats': a.device_stats} if engine is not None and not loader else {}), **({'curvature_flow': flow} if flow is not None else {}),

@@ -82,9 +82,9 @@ def main():
         res['note'] = 'host statement only: not measured on the GPU'
     else:
         import torch
-        from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+        from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
         assert torch.cuda.is_available(), 'crops_bench needs the GPU (or --host-only)'
-        eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+        eng = DeviceOps()
         res['device'] = torch.cuda.get_device_name(0)
         res['device_with_upload'] = stats(timed(lambda: device_crops(eng, img, lab), a.reps, 3))
         imd, lbd = torch.from_numpy(img).to(eng.device), torch.from_numpy(lab).to(eng.device)

@@ -3,10 +3,10 @@
 import sys, time
 import numpy as np, torch, scipy.ndimage
 sys.path.insert(0, '.')
-from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
 from unsupervised_anomaly_detection_brain_mri_amd.trainers import Metrics
 
-eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+eng = DeviceOps()
 rng = np.random.default_rng(0)
 D, H, W = 110, 128, 128
 

@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils.curvature_flow import curvature_flow  # noqa: E402
 
 SHAPES = ((110, 217, 181), (192, 512, 512))
@@ -54,7 +54,7 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'flow_bench needs the GPU'
-    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    eng = DeviceOps()
     res = {'workload': f'curvature flow, {ITERATIONS} iterations, time step {TIME_STEP}, spacing {list(SPACING)}, fp64 volumes', 'numpy': np.__version__,
            'device': torch.cuda.get_device_name(0), 'cases': {}}
 

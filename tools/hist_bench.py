@@ -25,7 +25,7 @@ import torch  # noqa: E402
 
 from tools.select_bench import timed  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd import _lib  # noqa: E402
-from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils import histograms  # noqa: E402
 
 S, NH, NW = 110, 256, 256
@@ -48,7 +48,7 @@ def main():
     ap.add_argument('--host-reps', type=int, default=3)
     ap.add_argument('--reps', type=int, default=20)
     a = ap.parse_args()
-    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    eng = DeviceOps()
     sync = lambda: torch.cuda.synchronize(eng.device)
     v, lab = volume()
     vd = eng._dev(v)

@@ -1,5 +1,5 @@
 """Times the lesion-wise evaluation ops on one seeded [110,256,256] prediction / ground-truth pair at about 2 % foreground: the device
-labelling (Engine.cc_label) and Engine.detection_rate with HIP events after a warm-up, and the host path they replace
+labelling (DeviceOps.cc_label) and DeviceOps.detection_rate with HIP events after a warm-up, and the host path they replace
 (Evaluation.compute_detection_rate on the downloaded volumes: three scipy labellings per 20-slice chunk), download included.
 For cc_label the algorithmic minimum traffic (one read of the volume, one write of the labels: 8 bytes per voxel) over its time is
 reported as a fraction of what a plain device copy of the same 8 bytes per voxel reaches in the same run.
@@ -20,7 +20,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine                      # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps               # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation                   # noqa: E402
 
 SHAPE = (110, 256, 256)
@@ -53,7 +53,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('lesionwise_bench needs a GPU: nothing is measured without one')
-    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    eng = DeviceOps()
     rng = np.random.default_rng(7)
     gt = blobs(rng, SHAPE, 0.02)
     lab, n = scipy.ndimage.label(gt, structure=np.ones((3, 3, 3), bool))

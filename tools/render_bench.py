@@ -97,9 +97,9 @@ def main():
         res['note'] = 'host statement and PNG encoding only: not measured on the GPU'
     else:
         import torch
-        from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine
+        from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps
         assert torch.cuda.is_available(), 'render_bench needs the GPU (or --host-only)'
-        eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+        eng = DeviceOps()
         res['device'] = torch.cuda.get_device_name(0)
         res['device_with_upload'] = stats(timed(lambda: device_render(eng, w), a.reps, 3))
         wd = {k: torch.from_numpy(v).to(eng.device) for k, v in w.items()}

@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils import Evaluation  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils.default_config_setup import get_options  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils.synthetic import SyntheticPatientDataset, synthetic_slices  # noqa: E402
@@ -111,7 +111,7 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'resample_bench needs the GPU'
-    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    eng = DeviceOps()
     x4, lab, msk = synthetic_slices(S, NH, NW, seed=7, lesions=True)
     x, seg, skull = x4[..., 0].astype(np.float64), lab.astype(int), msk.astype(int)
     sub = np.clip(scipy.ndimage.gaussian_filter(np.random.default_rng(3).random((S, R, R)), 1.0) - 0.45, 0, None).astype(np.float32)

@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils.synthetic import synthetic_slices  # noqa: E402
 
 S, R = 110, 128
@@ -66,7 +66,7 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'rotate_bench needs the GPU'
-    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    eng = DeviceOps()
     x4, lab, _ = synthetic_slices(S, R, R, seed=7, lesions=True)
     x, lab = np.ascontiguousarray(x4[..., 0], np.float32), (np.asarray(lab) > 0).astype(np.float32)
     res = {'workload': f'{S} slices of {R}x{R}, rotations {list(ROTATIONS)}: image (constant) + label map (nearest, fp32)', 'scipy': scipy.__version__,

@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from unsupervised_anomaly_detection_brain_mri_amd.engine import Engine  # noqa: E402
+from unsupervised_anomaly_detection_brain_mri_amd.device_ops import DeviceOps  # noqa: E402
 from unsupervised_anomaly_detection_brain_mri_amd.utils import nifti  # noqa: E402
 
 S, NH, NW = 110, 217, 181
@@ -79,7 +79,7 @@ def main():
     ap.add_argument('--host-reps', type=int, default=3)
     ap.add_argument('--reps', type=int, default=20)
     a = ap.parse_args()
-    eng = Engine('AE', 32, 32, 1, 8, 16, max_batch=1)
+    eng = DeviceOps()
     sync = lambda: torch.cuda.synchronize(eng.device)
     res = {'device': torch.cuda.get_device_name(eng.device), 'numpy': np.__version__, 'cases': {}}
 

@@ -7,20 +7,18 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _DevArray, _EvalOps, _ptr
+from .engine import _Handle, _ptr
 
 GROUPS = {'Encoder': _lib.GAN_ENCODER, 'Generator': _lib.GAN_GENERATOR, 'Discriminator': _lib.GAN_DISCRIMINATOR,
           'VAE': _lib.GAN_GROUP_VAE}       # 'VAE': the Encoder + Generator slice (AnoVAE-GAN's optim_vae), buffers / all-reduce only
 
 
-class GanEngine(_EvalOps):
+class GanEngine(_Handle):
+    _PREFIX = 'uad_gan_'
+
     def __init__(self, height=128, width=128, channels=1, inter_res=8, zdim=128, max_batch=64, scale=10.0, kappa=1.0,
                  device=None, math='bf16x3', variant='unified', dim=64, kl_weight=1.0, aae_kind='aae', rho=1.0, dim_w=1, c_lambda=1.0):
-        self.lib = _lib.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError('uad_hip needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback')
-        self.device = torch.device(device if device is not None else f'cuda:{torch.cuda.current_device()}')
-        torch.cuda.set_device(self.device)
+        super().__init__(device)
         self.h, self.w, self.c, self.inter, self.zdim, self.max_batch = height, width, channels, inter_res, zdim, max_batch
         variants = {'unified': _lib.GAN_UNIFIED, 'resnet': _lib.GAN_RESNET, 'anovaegan': _lib.GAN_ANOVAEGAN, 'aae': _lib.GAN_AAE}
         kinds = {'constrained_ae': 0, 'aae': 1, 'constrained_aae': 2, 'gmvae': 3, 'vae_zimmerer': 4, 'cevae_zimmerer': 5, 'gmvae_you': 6, 'caae_chen': 7}     # 'gmvae': zdim = dim_z, dim = dim_c, dim_w, c_lambda
@@ -33,36 +31,14 @@ class GanEngine(_EvalOps):
         cfg = _lib.UadGanConfig(height, width, channels, inter_res, zdim, max_batch, float(scale), float(kappa), variants[variant],
                                 int(dim), float(kl_weight), kinds.get(aae_kind, 1), float(rho), int(dim_w), float(c_lambda))
         self.dim_w, self.dim_c = int(dim_w), int(dim)
-        h = C.c_void_p()
-        _lib.check(self.lib.uad_gan_create(C.byref(cfg), C.byref(h)))
-        self.handle = h
-        self.nparams = int(self.lib.uad_gan_param_count(h))
-        self.spec = []
-        name = C.create_string_buffer(160)
-        off, rank, shape = C.c_longlong(), C.c_int(), (C.c_int * 4)()
-        for i in range(self.lib.uad_gan_num_tensors(h)):
-            _lib.check(self.lib.uad_gan_tensor_info(h, i, name, 160, C.byref(off), C.byref(rank), shape))
-            self.spec.append((name.value.decode(), tuple(shape[:rank.value]), int(off.value)))
+        self._create(cfg)
         dec_dense = {'constrained_ae': 'Bottleneck/dense_1/kernel', 'aae': 'Bottleneck/dense_1/kernel', 'constrained_aae': 'Decoder/dense/kernel',
                      'gmvae': 'Bottleneck/dense_4/kernel', 'vae_zimmerer': 'dense_2/kernel', 'cevae_zimmerer': 'Bottleneck/dense_2/kernel', 'caae_chen': 'Decoder/dense/kernel'}
         if variant == 'aae' and aae_kind == 'gmvae_you':        # fully convolutional: no dense decoder input
             self.flat = None
         else:
             self.flat = [s for n, s, _ in self.spec if n == (dec_dense[aae_kind] if variant == 'aae' else 'Generator/dense/kernel')][0][1]
-        self._views = {}
         self.set_math(math)
-
-    def close(self):
-        if getattr(self, 'handle', None):
-            torch.cuda.synchronize(self.device)
-            self.lib.uad_gan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_math(self, math):
         # 'bf16x3_all' (ResNet graph): also the generic k3 / k1 contractions in bf16x3 -- faster, but NOT parity-rated (header)
@@ -72,48 +48,14 @@ class GanEngine(_EvalOps):
         _lib.check(self.lib.uad_gan_set_math_mode(self.handle, modes[math]))
         self.math = math
 
-    # ---------------------------------------------------------------- buffers
-    def buffer(self, which=_lib.BUF_PARAMS):
-        # Every access of the parameter buffer goes through the library: uad_gan_buffer(PARAMS) waits for a weight repack still running on the
-        # handle's side stream and marks the packed copies stale, so a write through the (cached) view -- a second DP broadcast, a checkpoint
-        # restore -- can neither race with the repack nor leave the next forward on old packed kernels.
-        if which not in self._views or which == _lib.BUF_PARAMS:
-            ptr = self.lib.uad_gan_buffer(self.handle, which)
-            if which not in self._views:
-                self._views[which] = torch.as_tensor(_DevArray(ptr, self.nparams), device=self.device)
-        return self._views[which]
+    # ---------------------------------------------------------------- groups
+    def _gid(self, group):
+        return _lib.GAN_GENERATOR if (self.variant == 'aae' and group == 'AE') else GROUPS.get(group, group)
 
     def group(self, group):
         off, cnt = C.c_longlong(), C.c_longlong()
-        gid = _lib.GAN_GENERATOR if (self.variant == 'aae' and group == 'AE') else GROUPS.get(group, group)
-        _lib.check(self.lib.uad_gan_group(self.handle, gid, C.byref(off), C.byref(cnt)))
+        _lib.check(self.lib.uad_gan_group(self.handle, self._gid(group), C.byref(off), C.byref(cnt)))
         return int(off.value), int(cnt.value)
-
-    def set_params(self, params):
-        if isinstance(params, dict):
-            flat = np.concatenate([np.asarray(params[n], np.float32).reshape(-1) for n, _, _ in self.spec])
-        else:
-            flat = np.ascontiguousarray(params, np.float32).reshape(-1)
-        _lib.check(self.lib.uad_gan_set_buffer(self.handle, _lib.BUF_PARAMS, flat.ctypes.data_as(C.c_void_p), flat.size))
-
-    def get_buffer_host(self, which=_lib.BUF_PARAMS):
-        torch.cuda.synchronize(self.device)
-        out = np.empty(self.nparams, np.float32)
-        _lib.check(self.lib.uad_gan_get_buffer(self.handle, which, out.ctypes.data_as(C.c_void_p), out.size))
-        return out
-
-    def set_buffer_host(self, which, flat):
-        flat = np.ascontiguousarray(flat, np.float32).reshape(-1)
-        _lib.check(self.lib.uad_gan_set_buffer(self.handle, which, flat.ctypes.data_as(C.c_void_p), flat.size))
-
-    def unflatten(self, flat):
-        return {n: flat[o:o + int(np.prod(s))].reshape(s) for n, s, o in self.spec}
-
-    def get_params(self):
-        return self.unflatten(self.get_buffer_host(_lib.BUF_PARAMS))
-
-    def get_grads(self):
-        return self.unflatten(self.get_buffer_host(_lib.BUF_GRADS))
 
     def reset_optimizer(self):
         zeros = np.zeros(self.nparams, np.float32)
@@ -125,36 +67,15 @@ class GanEngine(_EvalOps):
         for g in ('Encoder', 'Generator', 'Discriminator'):
             self.set_step_count(g, 0)
 
-    def _gid(self, group):
-        return _lib.GAN_GENERATOR if (self.variant == 'aae' and group == 'AE') else GROUPS.get(group, group)
-
     def step_count(self, group):
         return int(self.lib.uad_gan_get_step(self.handle, self._gid(group)))
 
     def set_step_count(self, group, t):
         _lib.check(self.lib.uad_gan_set_step(self.handle, self._gid(group), int(t)))
 
-    def debug_buffer(self, name):
-        """tests: torch view of a named intermediate of the last phase."""
-        ptr, cnt = C.c_void_p(), C.c_longlong()
-        _lib.check(self.lib.uad_gan_debug_buffer(self.handle, name.encode(), C.byref(ptr), C.byref(cnt)))
-        return torch.as_tensor(_DevArray(ptr.value, cnt.value), device=self.device)
-
     def _new(self, shape, zero=False):
         shape = (shape,) if isinstance(shape, int) else tuple(shape)
         return (torch.zeros if zero else torch.empty)(shape, device=self.device, dtype=torch.float32)
-
-    def _dev(self, a, shape=None):
-        if a is None:
-            return None
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.float32))
-        t = t.to(self.device, torch.float32).contiguous()
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError(f'expected shape {tuple(shape)}, got {tuple(t.shape)}')
-        return t
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---------------------------------------------------------------- phases
     def aae_phase(self, which, x, z=None, eps=None, mask_z=None, mask_dec=None, mask_rec=None, want_backward=True, want_images=True,
@@ -348,14 +269,12 @@ class GanEngine(_EvalOps):
         """uad_gan_allreduce_attach: comm = a parallel.RcclComm (None detaches).  From then on phase(..., want_backward=True) all-reduces the trained group's
         gradient slice itself, in buckets issued while its backward still runs; adam(..., grad_scale=1 / world) follows on the same stream.
         Raises for the AAE-family graphs (their caller all-reduces the slice)."""
-        import ctypes as C
         _lib.check(self.lib.uad_gan_allreduce_attach(self.handle, C.c_void_p(comm.handle) if comm is not None else None, int(world)))
         self._ar_comm = comm
 
     def adam(self, group, lr, beta1=0.5, beta2=0.9, eps=1e-8, grad_scale=1.0):
         """group: 'Encoder' | 'Generator' | 'Discriminator'; for the AAE family 'AE' (= optim_ae), 'Discriminator', 'Encoder' (= optim_gen)."""
-        gid = _lib.GAN_GENERATOR if (self.variant == 'aae' and group == 'AE') else GROUPS[group]
-        _lib.check(self.lib.uad_gan_adam(self.handle, gid, lr, beta1, beta2, eps, grad_scale, self._stream()))
+        _lib.check(self.lib.uad_gan_adam(self.handle, self._gid(group), lr, beta1, beta2, eps, grad_scale, self._stream()))
 
     def reconstruct(self, x, mask_z=None, mask_g=None, want_l1=False, eps=None, mask_sigma=None):
         n = x.shape[0]

@@ -347,7 +347,7 @@ def _zoom_output_hw(shape, zf):
 
 
 def _prior_quantile(data, engine):
-    """np.quantile(data, 0.9) (utils/Evaluation.py:205); through the device select (engine._EvalOps.quantile) when the engine has it and
+    """np.quantile(data, 0.9) (utils/Evaluation.py:205); through the device select (device_ops.DeviceOps.quantile) when the engine has it and
     the volume's values are float32 numbers -- the op returns numpy's value and dtype.  Other data keep the host statement."""
     quantile = getattr(engine, 'quantile', None)
     if quantile is not None:
@@ -363,7 +363,7 @@ def collect_patient_volume(datasetObj, patient, nii_filename, options, engine=No
     options.axis; zoom every slice to options.sliceResolution -- cubic spline for the image (scipy.ndimage.zoom default order 3), the same
     call with mode='nearest' for the integer label / skull maps, exactly as written there.  Returns (x [S,H,W] float64, seg [S,H,W] int,
     skullmap [S,H,W] int, prior_quantile of the whole loaded volume, slice indices) or None when the volume is too thin (:210-211).
-    engine: an engine with the device `zoom` op (engine._EvalOps.zoom) -- the three maps of the patient are stacked and resampled in three
+    engine: an engine with the device `zoom` op (device_ops.DeviceOps.zoom) -- the three maps of the patient are stacked and resampled in three
     batched device calls (image: 'constant', fp32; label / skull: 'nearest', int32) and downloaded; None = the host loop above.  With an
     engine that has the device order statistics the prior quantile is one select call (_prior_quantile)."""
     o = datasetObj.options
@@ -445,7 +445,7 @@ def export_patient_volume(datasetObj, patient, nii_filename, subvolume, idx, sam
 
 
 def _render_ops(engine):
-    """(gray, heatmap, overlay, download): the device render ops of an engine that has them (engine._EvalOps.render_*), else the host statement
+    """(gray, heatmap, overlay, download): the device render ops of an engine that has them (device_ops.DeviceOps.render_*), else the host statement
     utils/render.py on downloaded arrays (the host stand-in engines of the CPU tests).  The images are the same either way."""
     from . import render
     if all(hasattr(engine, k) for k in ('render_gray', 'render_heatmap', 'render_overlay')):

@@ -19,7 +19,7 @@ at offset d and c = p(0):
     u'      = c + upd * time_step
 
 Every operation is one IEEE fp64 add, multiply or divide in the order written (sums run left to right from 0.0), with no fused
-multiply-add -- numpy has none -- so that the device kernel (csrc/uad_flow.hip, engine._EvalOps.curvature_flow), which is compiled with
+multiply-add -- numpy has none -- so that the device kernel (csrc/uad_flow.hip, device_ops.DeviceOps.curvature_flow), which is compiled with
 contraction off, returns the same bits.  This module is the reference every test of that kernel compares against, and the path
 nifti.volume_to_slices takes when no device engine is given."""
 import numpy as np

@@ -163,7 +163,7 @@ def _normalize_scaling_on(engine, v, lower, upper):
 
 def normalize_scaling(vol, lower=0, upper=99.8, engine=None):
     """NII.normalize(method='scaling', lowerpercentile, upperpercentile) (NII.py:50-66).
-    engine: an engine with the device order statistics (engine._EvalOps.select_quantiles / clamp_scale): both percentiles and the maximum
+    engine: an engine with the device order statistics (device_ops.DeviceOps.select_quantiles / clamp_scale): both percentiles and the maximum
     come from one device select call and the clamp-and-scale is one device pass; the same float32 array comes back.  The device path takes
     Python-scalar percentiles and NaN-free input (volume_to_slices zeroes NaNs first); an engine without the ops gets the host statement.
     Bit-equal to the host statement except for the SIGN of a zero that a zero-valued lower percentile clamps negative values to: numpy's
@@ -195,13 +195,13 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
     map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
-    engine: an engine with the device `zoom` op (engine._EvalOps.zoom): the kept, padded slices are resampled in one batched device call each
+    engine: an engine with the device `zoom` op (device_ops.DeviceOps.zoom): the kept, padded slices are resampled in one batched device call each
     for the image ('constant') and the label map ('nearest', fp32, then >= 0.9) instead of two scipy calls per slice.
-    device_stats (default: on when `engine` has the order-statistic ops, engine._EvalOps.select_quantiles): the masked volume is moved to
+    device_stats (default: on when `engine` has the order-statistic ops, device_ops.DeviceOps.select_quantiles): the masked volume is moved to
     slice-major order and uploaded ONCE as fp32, normalised there (_normalize_scaling_on), the empty-slice filter is one segmented select with
     one segment per slice, and the kept slices are padded and resampled from the device-resident volume -- no second upload of the image.
     The label path is unchanged.  Same kept slices and the same bits as device_stats=False.
-    device_rotate (default: on when `engine` has the `rotate` op, engine._EvalOps.rotate): the rotations run on the device -- the resampled
+    device_rotate (default: on when `engine` has the `rotate` op, device_ops.DeviceOps.rotate): the rotations run on the device -- the resampled
     batch stays there after engine.zoom, one rotate call for the images ('constant') and one for the label maps ('nearest', fp32; they are not
     thresholded again, as on the host) cover all non-zero angles, angle 0 passes through, center_crop is a slice of the result and both maps come
     back in ONE download -- instead of two scipy.ndimage.rotate calls per slice and angle.  Same order (slice-major, angle-minor); values
@@ -210,7 +210,7 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     NaN-zeroed fp64 volume BEFORE skull stripping, which is where MSLUB.py:242 calls it; spacing = (sx, sy, sz), the voxel size the filter
     scales its differences by (build_cache takes it from the NIfTI header).  The arithmetic is utils/curvature_flow.py's -- ITK's update written
     down from its source, not yet compared with SimpleITK's own output.  With an engine that has the `curvature_flow` op
-    (engine._EvalOps.curvature_flow) it runs there, same bits; with device_stats on, the skull-strip multiply and the move to slice-major order
+    (device_ops.DeviceOps.curvature_flow) it runs there, same bits; with device_stats on, the skull-strip multiply and the move to slice-major order
     happen on the device too, so the volume is uploaded once and not downloaded in between.  Without such an engine: the host statement.
     loader: 'mslub' (default) is everything above, the MS datasets' preparation.  'brainweb' is the training set's
     (dataloaders/BRAINWEB.py:125-185, 266-292; see _brainweb_to_slices): `seg` is the TISSUE-CLASS volume (values 0 .. 10) that supplies both
@@ -230,7 +230,7 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     as the label (BRAINWEB.py:173), here the label map is cropped: a stated deviation.
     Output order: slice-major, angle-minor, then the crops of that slice and angle in origin order (components in raster order of their first
     pixel; random crops in draw order); `kept` carries the slice index of every crop.
-    With an engine that has `region_props` and `crop` (engine._EvalOps) the prepared image batch and label batch stay on the device, the
+    With an engine that has `region_props` and `crop` (device_ops.DeviceOps) the prepared image batch and label batch stay on the device, the
     labels go through region_props(slab=1), the origins are formed on the host from the small table, one crop call serves the images and
     one the labels, and one download follows.  Without such an engine: the host statement.  The same crops bit for bit."""
     spec = _crop_setting(crops, center_crop, rotations)

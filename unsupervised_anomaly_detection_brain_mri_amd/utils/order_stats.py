@@ -9,7 +9,7 @@ bracket numpy's 'linear' virtual index (m - 1) * q.  Everything else is numpy's 
     np.float64 q gives a float64 index and, through gamma, a float64 result even for float32 data;
   * the interpolation: numpy.lib._function_base_impl._lerp -- a + (b - a) * t, replaced by b - (b - a) * (1 - t) where t >= 0.5 -- in the
     result type of (data, gamma).  `lo + (hi - lo) * g` alone is NOT what numpy returns.
-`OrderStatOps` is the mixin that turns an object with the three raw ops (select_quantiles, histogram_edges, clamp_scale: engine._EvalOps on
+`OrderStatOps` is the mixin that turns an object with the three raw ops (select_quantiles, histogram_edges, clamp_scale: device_ops.DeviceOps on
 the device, a numpy model in the CPU tests) into one with quantile / percentile / histogram."""
 import numpy as np
 

@@ -7,7 +7,7 @@ set-up for INTER_LINEAR, `resizeNN`), and it HAS NOT BEEN COMPARED WITH OPENCV'S
 fuse a multiply-add or order the two products differently, so even a correct restatement can differ from a given OpenCV build in the last
 bit.  What it was checked against: torch.nn.functional.interpolate in fp64 (`bilinear`, align_corners=False -- the same half-pixel
 coordinate rule; `nearest` where the fp64 index equals the integer formula) and a scalar, loop-written restatement of both functions
-(tests/test_resize_host.py); the device kernel (csrc/uad_resize.hip, engine._EvalOps.resize) is held to this module bit for bit.
+(tests/test_resize_host.py); the device kernel (csrc/uad_resize.hip, device_ops.DeviceOps.resize) is held to this module bit for bit.
 
 Per axis, with src -> dst samples:
 
