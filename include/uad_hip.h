@@ -30,6 +30,9 @@
  *       <- dataloaders/BRAINWEB.py:140-142 (cv2.resize of slices larger than sliceResolution), :266-289 (skull map from the tissue classes)
  *   uad_cc_props / uad_crop2d
  *       <- dataloaders/MSLUB.py:200-222 (cropType 'lesions': regionprops centroids, one crop per component), BRAINWEB.py:166-173 ('random')
+ *   uad_brain_boxes / uad_brain_boxes_f32 / uad_assemble_batch
+ *       <- trainers/CE.py:123-139 (retrieve_masked_batch: np.argwhere boxes, the 20x20 squares, batch * mask; called by CE.py:77, ceVAE.py:93),
+ *          dataloaders/BRAINWEB.py:459, MSLUB.py:468 (Options.addInstanceNoise in next_batch)
  *   uad_render_minmax_u8 / uad_render_heatmap / uad_render_overlay
  *       <- utils/Evaluation.py:302-321 (the per-slice PNGs: normalize_and_squeeze :368, squash_intensities + add_colorbar + utils.apply_colormap),
  *          :501-507 with utils/image_utils.py:22-45 (the TP / FP / FN overlay)
@@ -341,6 +344,32 @@ int uad_clock_probe(unsigned long long* out2, unsigned long long ticks_100mhz, v
 int uad_gather_slices(const float* src, const int* idx, int n, long long slice_elems, float* out, void* stream);
 int uad_gather_mask(const unsigned char* labels, const int* idx, int n, long long slice_px, const unsigned char* lut256, float* out,
                     void* stream);
+
+/* ---- context masking and instance noise of a batch (csrc/uad_batch.hip) --------------------------------------------------------
+ * uad_brain_boxes / uad_brain_boxes_f32  <- trainers/CE.py:124-126 (np.argwhere(brainmask): min / max row and column of the brain):
+ *   boxes[i] (DEVICE int32 [n,4]) = (row_min, row_max, col_min, col_max), both ends inclusive, of the non-zero pixels of slice i;
+ *   (-1, -1, -1, -1) for a slice that has none.  labels: DEVICE u8 [n, H*W] read through lut256 (DEVICE u8 [256]; NULL = the label value,
+ *   the uad_gather_mask convention), any base alignment; masks: DEVICE fp32 [n,H,W], non-zero = set (NaN counts, -0.0 does not).  One
+ *   launch, one workgroup a slice, integers only: the result does not depend on the order of execution.  UAD_ERR_INVALID: a non-positive
+ *   size, a NULL input / boxes.  UAD_ERR_UNSUPPORTED: H * W >= 2^31.
+ * uad_assemble_batch  <- dataloaders/BRAINWEB.py:411-459 (next_batch: the slice gather, :459 + numpy.random.normal(0, 0.01) under
+ *   Options.addInstanceNoise; MSLUB.py:468 and the other loaders alike) and trainers/CE.py:128-139 (the squares zeroed, batch * mask):
+ *     out_x[b]  = src[idx ? idx[b] : b]  (+ sigma * N(0,1) when sigma != 0)
+ *     out_ce[b] = out_x[b] * m_b
+ *   src: DEVICE fp32 [N,H,W,C]; idx: DEVICE int32 [n] or NULL (entries outside [0, N) are the caller's error); out_x / out_ce: DEVICE fp32
+ *   [n,H,W,C], either may be NULL but not both.  rects: DEVICE int32 [n,3,4], up to three windows (row, col, height, width) a sample,
+ *   height == 0 = unused; given exactly when out_ce is.  m_b is 0.0f inside any window of sample b (all channels), 1.0f elsewhere, and the
+ *   product is an fp32 multiply as the host's batch * mask: -x under a window gives -0.0, NaN stays NaN.  Windows that leave the slice are
+ *   the caller's error (DeviceOps.assemble_batch validates them on the host); they are only compared with, never used as addresses.
+ *   Noise: the numbers uad_rng_fill writes for kind UAD_RNG_NORMAL, per_sample = H*W*C and the same (seed, step, sample0, stream id =
+ *   rng_stream), element for element, added as x + (sigma * n) in fp32 without a fused multiply-add; sample b is GLOBAL sample sample0 + b.
+ *   With sigma == 0 out_x holds the source words.  One launch, no workspace, no atomics, nothing written outside out_x / out_ce.
+ *   UAD_ERR_INVALID: a non-positive size, H*W*C not a multiple of 4, sigma negative or not finite, sample0 < 0, NULL src, no output, out_ce
+ *   without rects or rects without out_ce, an output aliasing src or the other output.  UAD_ERR_UNSUPPORTED: n > 65535. */
+int uad_brain_boxes(const unsigned char* labels, int n, int H, int W, const unsigned char* lut256, int* boxes, void* stream);
+int uad_brain_boxes_f32(const float* masks, int n, int H, int W, int* boxes, void* stream);
+int uad_assemble_batch(const float* src, const int* idx, int n, int H, int W, int C, const int* rects, float sigma, unsigned long long seed,
+                       unsigned long long step, long long sample0, int rng_stream, float* out_x, float* out_ce, void* stream);
 
 /* ---- cubic-spline slice resampling (utils/Evaluation.py:223-232, 323-334; the slice ingestion of the dataloaders) ------------
  * uad_zoom_spline3: scipy.ndimage.zoom(a, (H/h, W/w), order=3, mode=..., prefilter=True, grid_mode=False) of every [h,w] slice of an

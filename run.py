@@ -33,7 +33,7 @@ def main(args):
     if args.cache:
         # a slice cache built from real volumes (tools/build_cache.py, utils/nifti.py): HBM-resident training set, per-patient TEST volumes
         from unsupervised_anomaly_detection_brain_mri_amd.utils.slice_cache import DeviceDataset
-        dataset_hc = DeviceDataset.from_cache(args.cache)
+        dataset_hc = DeviceDataset.from_cache(args.cache, instance_noise=args.instance_noise)
         if tuple(dataset_hc.shape[1:3]) != (args.outputHeight, args.outputWidth):
             raise SystemExit(f'cache slices are {dataset_hc.shape[1]}x{dataset_hc.shape[2]}, but -g/-w ask for {args.outputHeight}x{args.outputWidth}')
     else:
@@ -43,6 +43,7 @@ def main(args):
     for arg in vars(args):
         if hasattr(config, arg):
             setattr(config, arg, getattr(args, arg))
+    config.contextMaskPerSample = bool(args.context_mask_per_sample)
     model = trainer(None, config, network=network)
     model.train(dataset_hc)
     if args.threshold:
@@ -137,6 +138,10 @@ def build_parser():
     ap.add_argument('-d', '--ds', default=None, type=str)
     ap.add_argument('-n', '--numMonteCarloSamples', default=0, type=int)
     ap.add_argument('--cache', default=None, type=str, help='slice-cache directory (tools/build_cache.py) to train / evaluate on instead of the synthetic set')
+    ap.add_argument('--instance-noise', default=0.0, type=float, metavar='SIGMA',
+                    help='with --cache: N(0, SIGMA^2) noise added to every batch on the device (the loaders\' Options.addInstanceNoise uses 0.01); 0 = none')
+    ap.add_argument('--context-mask-per-sample', action='store_true',
+                    help='CE / ceVAE: mask every sample with its own squares instead of the last sample\'s (the reference\'s behaviour, the default)')
     # GMVAE-only flags (reference run.py:144-150, same defaults)
     ap.add_argument('-C', '--dim_c', default=9, type=int, help='only for GMVAE')
     ap.add_argument('-Z', '--dim_z', default=128, type=int, help='only for GMVAE')

@@ -2,8 +2,9 @@
 // that is include/uad_hip.h).  All pointers are device pointers, all tensors are
 // fp32 NHWC, all launches are asynchronous on the given stream.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#ifndef UAD_HOST_EMULATION      // a host emulation of tests/native/ takes only the generator at the end of this file
+#include <hip/hip_runtime.h>
 
 // records the message uad_last_error() returns and hands `code` back (uad_model.hip); the entry points' `return fail(...)`
 int uad_fail(int code, const char* fmt, ...);
@@ -349,3 +350,36 @@ void uad_launch_adam(float* p, const float* g, float* m, float* v, size_t n, flo
 // zeroed where x < prior_thresh (pass -inf to disable); per-sample sum|x-xr| into l1err[n] (may be null)
 void uad_launch_residual(const float* x, const float* xr, const float* mask, int n, int hw, int pos_only,
                          float prior_thresh, float* out, float* l1err, hipStream_t st);
+#endif  // UAD_HOST_EMULATION
+
+// ---- the counter-based generator of uad_rng_fill (uad_misc.hip: rng_fill_kernel) and uad_assemble_batch (uad_batch.hip) ----
+// Philox4x32-10 keyed by the run seed; oracle/rng.py is the CPU statement.  Inline, so that both kernels form the same bits.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// the four words of element quad e4 of GLOBAL sample gs at a step: counter = (e4, gs, step, stream id)
+__device__ __forceinline__ void uad_rng_quad(unsigned e4, unsigned long long gs, unsigned step_lo, unsigned step_hi, int stream, unsigned k0, unsigned k1,
+                                             unsigned r[4]) {
+    philox4x32_10(e4, (unsigned)gs, step_lo, (step_hi << 8) ^ ((unsigned)(gs >> 32) << 16) ^ (unsigned)stream, k0, k1, r);
+}
+// Box-Muller on two 24-bit uniforms: two words -> the N(0,1) pair (rad * cos, rad * sin).  The pragma pins the contraction mode of this body to
+// HIP's default, whatever -ffp-contract the including file is built with, and the logarithm is the builtin the HIP math header's logf
+// wraps, called HERE so that the call carries this body's mode: the compiler's expansion of it inherits the mode of the call and fuses two
+// multiply-adds under the default, so a file built with -ffp-contract=off (uad_batch.hip) would otherwise form other last bits than
+// rng_fill_kernel.
+__device__ __forceinline__ void uad_box_muller(unsigned ra, unsigned rb, float& a, float& b) {
+#pragma clang fp contract(fast)
+    const float u1 = ((float)(ra >> 8) + 1.0f) * 5.9604644775390625e-8f;       // (0, 1]
+    const float u2 = (float)(rb >> 8) * 5.9604644775390625e-8f;                // [0, 1)
+    const float rad = sqrtf(-2.0f * __builtin_logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    a = rad * cs; b = rad * sn;
+}

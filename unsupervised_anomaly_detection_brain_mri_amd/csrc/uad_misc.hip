@@ -970,16 +970,7 @@ void uad_launch_spatial_z_bwd(const float* dz, const float* c, const float* gamm
 // (u >= rate ? 1/(1-rate) : 0, nn.dropout's rule).  One launch fills every array of the step (grid.y = job).
 // ------------------------------------------------------------------------------------------------
 namespace {
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// philox4x32_10, uad_rng_quad and uad_box_muller live in uad_kernels.h: uad_batch.hip adds the same numbers to a batch
 struct RngJobs { UadRngJob j[8]; };
 __global__ void __launch_bounds__(256) rng_fill_kernel(RngJobs jobs, int n, unsigned k0, unsigned k1, unsigned step_lo, unsigned step_hi,
                                                        long long sample0) {
@@ -990,18 +981,11 @@ __global__ void __launch_bounds__(256) rng_fill_kernel(RngJobs jobs, int n, unsi
         const int s = (int)(q / quads), e4 = (int)(q % quads);
         const unsigned long long gs = (unsigned long long)(sample0 + s);
         unsigned r[4];
-        philox4x32_10((unsigned)e4, (unsigned)gs, step_lo, (step_hi << 8) ^ ((unsigned)(gs >> 32) << 16) ^ (unsigned)jb.stream, k0, k1, r);
+        uad_rng_quad((unsigned)e4, gs, step_lo, step_hi, jb.stream, k0, k1, r);
         float v[4];
         if (jb.kind == 0) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const float u1 = ((float)(r[2 * h] >> 8) + 1.0f) * 5.9604644775390625e-8f;       // (0, 1]
-                const float u2 = (float)(r[2 * h + 1] >> 8) * 5.9604644775390625e-8f;            // [0, 1)
-                const float rad = sqrtf(-2.0f * logf(u1));
-                float sn, cs;
-                sincosf(6.283185307179586f * u2, &sn, &cs);
-                v[2 * h] = rad * cs; v[2 * h + 1] = rad * sn;
-            }
+            for (int h = 0; h < 2; ++h) uad_box_muller(r[2 * h], r[2 * h + 1], v[2 * h], v[2 * h + 1]);
         } else {
             const float keep = 1.0f / (1.0f - jb.rate);
 #pragma unroll

@@ -39,6 +39,21 @@ def rotation_transform(angle, in_hw):
     return m, in_center - m @ in_center
 
 
+def check_rects(rects, n, h, w):
+    """The window table of assemble_batch / context_mask, validated on the host: integers [n,3,4] of (row, col, height, width), a window with
+    height 0 unused, every used one non-empty and inside the h x w slice -> contiguous int32 [n,3,4]; ValueError otherwise."""
+    r = np.asarray(rects)
+    if r.shape != (n, 3, 4) or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f'rects must be integers of shape [{n},3,4], got {r.dtype} {r.shape}')
+    r = r.astype(np.int64)
+    used = r[..., 2] != 0
+    bad = used & ((r[..., 0] < 0) | (r[..., 1] < 0) | (r[..., 2] < 0) | (r[..., 3] <= 0) | (r[..., 0] + r[..., 2] > h) | (r[..., 1] + r[..., 3] > w))
+    if bad.any():
+        b, k = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f'window {k} of sample {b} {tuple(int(v) for v in r[b, k])} leaves the {h} x {w} slice')
+    return np.ascontiguousarray(r, np.int32)
+
+
 class DeviceOps(OrderStatOps):
     """The device ops on one GPU; no model handle (close() is a no-op so that callers can treat it like an engine).
     quantile / percentile / histogram come from utils.order_stats.OrderStatOps over the raw ops select_quantiles / histogram_edges below."""
@@ -342,6 +357,91 @@ class DeviceOps(OrderStatOps):
             kk = min(65535, k - j0)
             _lib.check(self.lib.uad_crop2d(_ptr(s), n_in, h, w, _ptr(od[j0:j0 + kk]), kk, ch, cw, _ptr(out[j0:j0 + kk]), self._stream()))
         return out
+
+    # ---------------------------------------------------------------- context masking and instance noise of a batch (csrc/uad_batch.hip)
+    def brain_boxes(self, masks_or_labels, lut=None):
+        """The bounding box of the non-zero pixels of every slice (trainers/CE.py:124-126: np.argwhere of the brain mask) on the device
+        (uad_brain_boxes / uad_brain_boxes_f32) -> int32 device tensor [n,4] of (row_min, row_max, col_min, col_max), both ends inclusive,
+        (-1,-1,-1,-1) for a slice without a non-zero pixel.  A uint8 array / tensor [n,h,w] is a label store, read through `lut` ([256] uint8,
+        None = the label value); anything else is an fp32 mask [n,h,w] (a trailing channel axis of 1 is dropped), non-zero = set."""
+        a = masks_or_labels
+        if (a.dtype == torch.uint8) if isinstance(a, torch.Tensor) else (np.asarray(a).dtype == np.uint8):
+            lab = (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))).to(self.device).contiguous()
+            if lab.dim() != 3 or lab.numel() == 0:
+                raise ValueError(f'labels must be a non-empty [n,h,w], got {tuple(lab.shape)}')
+            lut_d = None
+            if lut is not None:
+                lut_d = lut if isinstance(lut, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(lut))
+                if lut_d.dtype != torch.uint8 or tuple(lut_d.shape) != (256,):
+                    raise ValueError(f'lut must be [256] uint8, got {tuple(lut_d.shape)} {lut_d.dtype}')
+                lut_d = lut_d.to(self.device).contiguous()
+            out = torch.empty((lab.shape[0], 4), device=self.device, dtype=torch.int32)
+            _lib.check(self.lib.uad_brain_boxes(_ptr(lab), lab.shape[0], lab.shape[1], lab.shape[2], _ptr(lut_d), _ptr(out), self._stream()))
+            return out
+        if lut is not None:
+            raise ValueError('lut goes with a uint8 label store')
+        m = self._f32_batch(a, 'masks')
+        if m.shape[0] == 0:
+            raise ValueError('masks must be a non-empty [n,h,w]')
+        out = torch.empty((m.shape[0], 4), device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.uad_brain_boxes_f32(_ptr(m), m.shape[0], m.shape[1], m.shape[2], _ptr(out), self._stream()))
+        return out
+
+    def assemble_batch(self, src, index=None, rects=None, noise=None, want_x=True):
+        """The batch and its context-masked companion in one device pass (uad_assemble_batch): x[b] = src[index[b]] (index None: src[b]) plus
+        sigma * N(0,1) with noise = (sigma, seed, step, sample0, stream) -- the numbers engine.rng_fill gives job `stream` of a call with the
+        same (seed, step, sample0); the reference's Options.addInstanceNoise, dataloaders/BRAINWEB.py:459 -- and x_ce[b] = x[b] * m_b with m_b
+        zero inside sample b's windows (trainers/CE.py:128-139).  src: fp32 [N,h,w,c] array / tensor; index: integer list, a HOST one is
+        validated, a device int32 tensor is taken as it is (DeviceDataset's own); rects: [n,3,4] integers (row, col, height, width), height 0 =
+        unused -- a host table is validated here (shape, every used window inside the slice), a device int32 tensor only for its shape.
+        -> (x, x_ce) device tensors [n,h,w,c]; x is None with want_x=False, x_ce is None without rects."""
+        s = self._f32(src, 'src must be a non-empty [N,h,w,c]', 4, nonempty=True)
+        N, h, w, c = s.shape
+        if (h * w * c) % 4:
+            raise ValueError(f'h * w * c must be a multiple of 4, got {h} x {w} x {c}')
+        idx, n = None, N
+        if index is not None:
+            if isinstance(index, torch.Tensor) and index.is_cuda:
+                if index.dtype != torch.int32 or index.dim() != 1:
+                    raise ValueError('a device index must be a 1-D int32 tensor')
+                idx = index.contiguous()
+            else:
+                host = np.asarray(index.numpy() if isinstance(index, torch.Tensor) else index)
+                if host.ndim != 1 or host.size == 0 or not np.issubdtype(host.dtype, np.integer):
+                    raise ValueError(f'index must be a non-empty 1-D integer list, got shape {host.shape} dtype {host.dtype}')
+                if host.min() < 0 or host.max() >= N:
+                    raise ValueError(f'index entries must lie in [0, {N}), got {int(host.min())} .. {int(host.max())}')
+                idx = torch.from_numpy(np.ascontiguousarray(host, np.int32)).to(self.device)
+            n = int(idx.numel())
+            if n == 0:
+                raise ValueError('index must not be empty')
+        rd = None
+        if rects is not None:
+            if isinstance(rects, torch.Tensor) and rects.is_cuda:
+                if rects.dtype != torch.int32 or tuple(rects.shape) != (n, 3, 4):
+                    raise ValueError(f'rects must be int32 [{n},3,4], got {rects.dtype} {tuple(rects.shape)}')
+                rd = rects.contiguous()
+            else:
+                rd = torch.from_numpy(check_rects(rects.numpy() if isinstance(rects, torch.Tensor) else rects, n, h, w)).to(self.device)
+        elif not want_x:
+            raise ValueError('nothing asked for: want_x=False without rects')
+        sigma, seed, step, sample0, stream = (0.0, 0, 0, 0, 0) if noise is None else noise
+        if not (0.0 <= float(sigma) < math.inf):
+            raise ValueError(f'sigma must be finite and >= 0, got {sigma!r}')
+        if int(sample0) < 0 or int(step) < 0:
+            raise ValueError('step and sample0 must be >= 0')
+        x = torch.empty((n, h, w, c), device=self.device, dtype=torch.float32) if want_x else None
+        x_ce = torch.empty((n, h, w, c), device=self.device, dtype=torch.float32) if rd is not None else None
+        for j0 in range(0, n, 65535):                                       # one grid holds 65535 samples
+            k = min(65535, n - j0)
+            part = lambda t: None if t is None else _ptr(t[j0:j0 + k])
+            _lib.check(self.lib.uad_assemble_batch(_ptr(s) if idx is not None else _ptr(s[j0:j0 + k]), part(idx), k, h, w, c, part(rd), float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step),
+                                                   int(sample0) + j0, int(stream), part(x), part(x_ce), self._stream()))
+        return x, x_ce
+
+    def context_mask(self, batch, rects):
+        """batch * mask of trainers/CE.py:139 for a device batch [n,h,w,c] and its windows [n,3,4] -> the masked device tensor."""
+        return self.assemble_batch(batch, rects=rects, want_x=False)[1]
 
     # ---------------------------------------------------------------- 8-bit rendering of the sample images (csrc/uad_render.hip)
     def _f32_batch(self, a, what, shape=None):

@@ -9,7 +9,7 @@ from math import inf
 import numpy as np
 
 from .AEMODEL import AEMODEL, Phase, indicate_early_stopping
-from .CE import retrieve_masked_batch
+from .CE import masked_shard, retrieve_masked_batch      # noqa: F401 (retrieve_masked_batch: the name ceVAE.py:8 imports)
 
 
 class ceVAE(AEMODEL):
@@ -90,8 +90,7 @@ class ceVAE(AEMODEL):
         scalars = defaultdict(list)
         num_batches = self._num_batches(dataset, phase)
         for idx in range(num_batches):
-            batch, _, brainmasks = self._shard(dataset, phase, return_brainmask=True)
-            masked_batch = retrieve_masked_batch(batch, brainmasks)        # drawn in every phase, used in TRAIN only
+            batch, masked_batch = masked_shard(self, dataset, phase)        # drawn in every phase, used in TRAIN only
             run = self.step(batch, phase, masked_batch=masked_batch, fetch_maps=False)
             print(f'Epoch ({phase.value}): [{epoch:2d}] [{idx:4d}/{num_batches:4d}] loss: {run["loss"]:.8f}')
             for k, v in run.items():

@@ -11,7 +11,9 @@ In memory: `DeviceDataset` keeps the whole slice set in device memory (a Brainwe
 the reference's dataset duck-type (`num_batches`, `next_batch`) with DEVICE tensors: a batch is one gather kernel over an index
 vector (`uad_gather_slices` / `uad_gather_mask`), so a training step has no host-to-device copy.  The cursor / epoch-wrap /
 shuffle behaviour is `dataloaders/BRAINWEB.py:411-457` restated, including its quirk that the first epoch is never shuffled
-(`:419` compares the epoch dict with 0)."""
+(`:419` compares the epoch dict with 0).  `instance_noise` is the loaders' Options.addInstanceNoise (`:459`), added by the same launch that
+gathers the batch (`uad_assemble_batch`); the brain bounding boxes the context-encoder trainers draw their squares in (trainers/CE.py:124-126)
+are measured once over the whole label store (`uad_brain_boxes`) and kept on the host."""
 import ctypes as C
 import json
 import os
@@ -117,8 +119,17 @@ class BatchCursor:
 class DeviceDataset:
     """Dataset duck-type over an HBM-resident slice cache; batches are device tensors."""
     SET_TYPES = SET_TYPES
+    NOISE_STREAM = 64          # stream id of the instance noise in the generator's counter: the trainers' noise jobs of a step use 0 .. 7
 
-    def __init__(self, images, sets, labels=None, seed=0, device=None, patients=None):
+    def __init__(self, images, sets, labels=None, seed=0, device=None, patients=None, instance_noise=0.0):
+        """instance_noise: sigma of the N(0, sigma^2) noise every next_batch adds to the gathered batch, on any split (the reference's
+        Options.addInstanceNoise adds numpy.random.normal(0, 0.01) in next_batch regardless of `set`); 0 = none, and then next_batch launches
+        what it always did.  The noise is the counter-based generator's (uad_rng_fill's numbers): keyed by the dataset seed, a per-split batch
+        counter as the step and the position in the batch next_batch was asked for as the sample index -- the GLOBAL batch under data
+        parallelism, so every rank adds the same noise to the same slice."""
+        self.instance_noise = float(instance_noise)
+        if not 0.0 <= self.instance_noise < float('inf'):
+            raise ValueError(f'instance_noise must be finite and >= 0, got {instance_noise!r}')
         import torch
         from .. import _lib
         self._torch, self._lib = torch, _lib
@@ -137,6 +148,10 @@ class DeviceDataset:
         self._lut = torch.from_numpy(brainmask_lut()).to(self.device)
         sets = np.asarray(sets)
         self._set_idx = {name: np.where(sets == k)[0].astype(np.int32) for k, name in enumerate(SET_TYPES)}
+        self.seed = int(seed)
+        self._noise_step = {name: 0 for name in SET_TYPES}
+        self._boxes = None                     # host int32 [N,4], measured on first use (brain_boxes)
+        self._keep_host = None                 # cache rows of the most recent batch, beside self._keep
         rng = np.random.default_rng(seed)
         self._cursor = {name: BatchCursor(len(ix), rng) for name, ix in self._set_idx.items()}
         # batch indices travel host -> device through a ring of pinned staging buffers with non-blocking copies: `.to(device)` of a pageable
@@ -177,16 +192,52 @@ class DeviceDataset:
         ev.record(torch.cuda.current_stream(self.device))
         return dev[:n]
 
+    def upload_int32(self, arr):
+        """A small host integer table -> device int32 tensor of its shape through the pinned staging ring of the batch indices: a
+        non-blocking copy, ordered on the current stream; the tensor is valid until the ring comes round (64 uploads later)."""
+        arr = np.asarray(arr)
+        return self._indices_to_device(arr.reshape(-1)).view(arr.shape)
+
+    def brain_boxes(self, set=None):
+        """Host int32 [n,4] (row_min, row_max, col_min, col_max) of the brain mask -- the label store read through the brain-mask LUT -- of the
+        slices of split `set` in cache order (None: of every slice); (-1,-1,-1,-1) for a slice without brain.  The first call measures the
+        whole label store in one launch and downloads the N x 16 bytes once."""
+        if self._labels is None:
+            raise ValueError('this dataset holds no label maps: there is no brain mask to take bounding boxes of')
+        if self._boxes is None:
+            N, H, W, _ = self.shape
+            boxes = self._torch.empty((N, 4), device=self.device, dtype=self._torch.int32)
+            self._lib.check(self.lib.uad_brain_boxes(C.c_void_p(self._labels.data_ptr()), N, H, W, C.c_void_p(self._lut.data_ptr()),
+                                                     C.c_void_p(boxes.data_ptr()), self._stream()))
+            self._boxes = boxes.cpu().numpy()
+        return self._boxes if set is None else self._boxes[self._set_idx[set]]
+
+    def last_boxes(self):
+        """brain_boxes rows of the slices of the most recent next_batch call, in batch order; no device work after the first use."""
+        if self._labels is None:
+            raise ValueError('this dataset holds no label maps: there is no brain mask to take bounding boxes of')
+        if self._keep_host is None:
+            raise RuntimeError('last_boxes() before the first next_batch()')
+        return self.brain_boxes()[self._keep_host]
+
     def next_batch(self, batch_size, shuffle=True, set='TRAIN', return_brainmask=False):
         torch, _lib = self._torch, self._lib
         pos = self._cursor[set].next(batch_size, shuffle)
         assert pos.size, "The batch is empty!"
-        idx = self._indices_to_device(self._set_idx[set][pos])
+        rows = self._set_idx[set][pos]
+        idx = self._indices_to_device(rows)
         n = int(idx.numel())
         N, H, W, Cc = self.shape
         out = torch.empty((n, H, W, Cc), device=self.device, dtype=torch.float32)
-        _lib.check(self.lib.uad_gather_slices(C.c_void_p(self._images.data_ptr()), C.c_void_p(idx.data_ptr()), n, H * W * Cc,
-                                              C.c_void_p(out.data_ptr()), self._stream()))
+        if self.instance_noise > 0.0:         # gather + noise in one launch; sample b of the batch asked for is sample b of this step
+            step = self._noise_step[set]
+            self._noise_step[set] += 1
+            _lib.check(self.lib.uad_assemble_batch(C.c_void_p(self._images.data_ptr()), C.c_void_p(idx.data_ptr()), n, H, W, Cc, None,
+                                                   self.instance_noise, self.seed & 0xFFFFFFFFFFFFFFFF, step, 0, self.NOISE_STREAM,
+                                                   C.c_void_p(out.data_ptr()), None, self._stream()))
+        else:
+            _lib.check(self.lib.uad_gather_slices(C.c_void_p(self._images.data_ptr()), C.c_void_p(idx.data_ptr()), n, H * W * Cc,
+                                                  C.c_void_p(out.data_ptr()), self._stream()))
         labels = masks = None
         if self._labels is not None:
             labels = torch.empty((n, H, W), device=self.device, dtype=torch.float32)
@@ -196,5 +247,5 @@ class DeviceDataset:
                 masks = torch.empty((n, H, W), device=self.device, dtype=torch.float32)
                 _lib.check(self.lib.uad_gather_mask(C.c_void_p(self._labels.data_ptr()), C.c_void_p(idx.data_ptr()), n, H * W,
                                                     C.c_void_p(self._lut.data_ptr()), C.c_void_p(masks.data_ptr()), self._stream()))
-        self._keep = idx
+        self._keep, self._keep_host = idx, rows
         return out, labels, masks
