@@ -701,6 +701,33 @@ int uad_op_conv_d_bwdact(const uad_conv_desc_t* d, const float* small_in, const 
                          const uad_xform_t* act, float* big_out, float* s1, float* s2, void* stream);
 int uad_op_conv_w(const uad_conv_desc_t* d, const float* big, const uad_xform_t* xfb, const float* small_,
                   const uad_xform_t* xfs, float* dW, void* stream);
+/* Math mode of the op entry points: environment variable UAD_MATH, read per call.  Unset / "f32": exact fp32; "bf16x3": two bf16 planes; "bf16x6": a k5 s2
+ * launch runs on the three-plane spatial kernels wherever the library's own decision functions take it (three planes packed here), and on the exact-fp32 route with
+ * the fp32 pack everywhere else -- a refused three-plane route is a normal outcome, reported by uad_op_conv_plan, and never an abort.
+ *
+ * uad_op_conv_plan: host only, nothing is launched.  What the op entry point of `kind` ('F' | 'D' | 'W') would run for this descriptor in the current UAD_MATH.
+ * epi: UAD_OP_EPI_* (F / D).  xf_flags: UAD_OP_XF_* (F / D: activation on load of the input; W: of big / of small; F: final backward on load).  out[12]:
+ *   F / D: 0 .. 5 and 8 as uad_debug_plan (path, splits, slabs reduced in the kernel, column block, column-partial tiles, three-plane route 1 | 0 | -1, slab floats),
+ *          6 D-kind kernel generation of a spatial launch (1 lane = pixel | 2 class-sequential conv5_d16 | 3 conv5_bf16<KIND_D> fallback | 4 exact-fp32 conv5_d_kernel;
+ *          0: F kind or no spatial launch), 7 channel range per workgroup `cst` of generations 1 .. 3 (else 0), 9 1 when the entry point would answer
+ *          UAD_ERR_UNSUPPORTED (a fused final the shape or mode has no kernel for, a final backward on load outside its instances), 10 math mode (0 f32 | 1 bf16x3 |
+ *          3 bf16x6), 11 the fused final's tile: 16 (16 x 16 training instance) | 8 (8 x 16) | 0 (not a fused final);
+ *   W:     0 .. 5, 7, 8 as uad_debug_plan, 10 math mode, the rest 0. */
+enum { UAD_OP_EPI_BIAS = 0, UAD_OP_EPI_BWD_ACT = 1, UAD_OP_EPI_FINAL = 2, UAD_OP_EPI_FINAL_TRAIN = 3, UAD_OP_EPI_FINAL_DC = 4 };
+enum { UAD_OP_XF_IN = 1, UAD_OP_XF_SMALL = 2, UAD_OP_XF_FINAL_BWD = 4 };
+int uad_op_conv_plan(const uad_conv_desc_t* d, int kind, int epi, int xf_flags, long long* out);
+/* One D-kind launch with the fused final epilogue (the last decoder block): c = ConvT(xf(small_in)) + bias, a = lrelu_alpha(bn.scale * c + bn.shift), x_hat = a . wf + bf[0],
+ * l1 = |x_hat - x|.  x_hat [N,HB,WB] and rec_sum[1] = sum l1 are always written, l1 when non-null.  Forms: forward only (bits, dxhat, dc, red null); training, compressed
+ * (bits [N,HB,WB] words with bit ch = (BN output of channel ch > 0), dxhat = sign(x_hat - x) * inv_batch, red[3 CB + 1] = {d wf, S1 = sum d bn, S2 = sum d bn * c, d bf} summed
+ * over the tiles by the library's slab reduction; split-bf16 modes only); training, uncompressed (dc [N,HB,WB,CB] = d loss / d c, and red).  UAD_ERR_UNSUPPORTED where
+ * uad_op_conv_plan reports out[9] = 1.  Synchronous. */
+int uad_op_conv_d_final(const uad_conv_desc_t* d, const float* small_in, const uad_xform_t* xf, const float* W, const float* bias, const uad_xform_t* bn,
+                        const float* wf, const float* bf, const float* x, float inv_batch, float* x_hat, float* l1, float* rec_sum,
+                        unsigned* bits, float* dxhat, float* dc, float* red, void* stream);
+/* uad_op_conv_f with final backward on load: the big operand is the compressed loss gradient of uad_op_conv_d_final (bits, dxhat) expanded while it is staged,
+ * d loss / d c[pixel][ch] = dxhat[pixel] * wf[ch] * lrelu'(bit ch) * bn.scale[ch]; bias / mul / add as uad_op_conv_f.  Split-bf16 modes, CB <= 32. */
+int uad_op_conv_f_final_bwd(const uad_conv_desc_t* d, const unsigned* bits, const float* dxhat, const float* wf, const uad_xform_t* bn, const float* W,
+                            const float* bias, const float* mul, const float* add, float* small_out, void* stream);
 int uad_op_conv_first_fwd(const uad_conv_desc_t* d, const float* x, const float* W, const float* bias, float* out,
                           void* stream);
 int uad_op_conv_first_wgrad(const uad_conv_desc_t* d, const float* x, const float* g, float* dW, void* stream);

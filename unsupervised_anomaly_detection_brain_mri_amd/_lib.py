@@ -196,6 +196,12 @@ SYMBOLS = {
                                        C.POINTER(UadXform), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'uad_op_conv_w': (C.c_int, [C.POINTER(UadConvDesc), C.c_void_p, C.POINTER(UadXform), C.c_void_p,
                                 C.POINTER(UadXform), C.c_void_p, C.c_void_p]),
+    'uad_op_conv_plan': (C.c_int, [C.POINTER(UadConvDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    'uad_op_conv_d_final': (C.c_int, [C.POINTER(UadConvDesc), C.c_void_p, C.POINTER(UadXform), C.c_void_p, C.c_void_p, C.POINTER(UadXform),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_op_conv_f_final_bwd': (C.c_int, [C.POINTER(UadConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(UadXform), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'uad_op_conv_first_fwd': (C.c_int, [C.POINTER(UadConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     'uad_op_conv_first_wgrad': (C.c_int, [C.POINTER(UadConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

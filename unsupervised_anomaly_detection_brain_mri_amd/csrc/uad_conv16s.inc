@@ -75,13 +75,21 @@ __global__ void __launch_bounds__(64 * WGM * WGN) __attribute__((amdgpu_waves_pe
     // accumulators per fragment.  Round 5: ONE (the three products of a unit chain into the same accumulator).  With three (round 3: "one fragment alone
     // needs independent chains") every parity class ended with 32 v_add per wave to fold them -- 128 of a wave's ~900-2000 VALU instructions in kernels whose time
     // tracks their VALU count (tools/issue_ubench.hip) -- while the SIMD's second wave already fills the matrix pipe between two dependent MFMAs of this one.
-    constexpr int NACC = UAD_D16S_NACC;
+    // Three planes (bf16x6) keep TWO: the leading product in one, the five correction products in the other.  Measured per launch (tests/test_gpu_ops_spatial.py,
+    // DESIGN section 23): chained into the accumulator of the leading product, the corrections left every output element ~4.5e-9 of the tensor max too low (the
+    // rms error of the exact-fp32 kernel, but a one-sided mean: small products folded into a large accumulator lose their low bits in one direction), which a column
+    // sum over 32768 elements turns into 3.4e-6 -- six times the exact-fp32 kernel's S1 error.  In an accumulator of their own magnitude the loss is 2^-8 of that.
+    // (Three accumulators, conv5_f16_kernel's form, cure it too but do not fit under the 256 registers of two waves per SIMD: seven instances spilled.  Two fit once
+    // the activation-backward epilogue stops holding its cprev prefetch through the class: PREF below.)
+    constexpr int NACC = (NPL == 3 && MF == 1) ? 2 : UAD_D16S_NACC;
+    constexpr int C1 = NACC > 1 ? 1 : 0, C2 = NACC == 3 ? 2 : C1;      // accumulators of the w_lo a_hi family and of the w_hi a_lo family
+    constexpr bool PREF = NACC == 1;                                  // BWD: request cprev when the class starts (16 registers held through it) or at its end
     constexpr bool FIN = EPI == UAD_EPI_FINAL, BWD = EPI == UAD_EPI_BWD_ACT, PLAIN = EPI == UAD_EPI_BIAS;
     constexpr int FL = 3 * 32 + 2;              // floats of one wave's partial-sum row
     static_assert(TH * TW == 32 * MF * WGM, "MF 32-pixel fragments per wave along M");
     static_assert(CST % 32 == 0, "32-channel weight-fragment units");
     static_assert(MF == 1 || MF == 2, "one or two fragments per wave");
-    static_assert(NACC == 1 || (NACC == 3 && MF == 1), "three accumulators only with one fragment per wave");
+    static_assert(NACC == 1 || ((NACC == 2 || NACC == 3) && MF == 1), "several accumulators only with one fragment per wave");
     static_assert(!FIN || WGN == 1, "the fused final conv needs every output channel of a pixel in one wave");
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
     constexpr int PLANE = IH * IW * LDH;
@@ -384,7 +392,12 @@ __global__ void __launch_bounds__(64 * WGM * WGN) __attribute__((amdgpu_waves_pe
             float4 v[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                if constexpr (NACC == 3) {
+                if constexpr (NACC == 2) {
+                    v[g].x = acc[f][0][4 * g + 0] + acc[f][1][4 * g + 0];
+                    v[g].y = acc[f][0][4 * g + 1] + acc[f][1][4 * g + 1];
+                    v[g].z = acc[f][0][4 * g + 2] + acc[f][1][4 * g + 2];
+                    v[g].w = acc[f][0][4 * g + 3] + acc[f][1][4 * g + 3];
+                } else if constexpr (NACC == 3) {
                     v[g].x = acc[f][0][4 * g + 0] + (acc[f][1][4 * g + 0] + acc[f][2][4 * g + 0]);
                     v[g].y = acc[f][0][4 * g + 1] + (acc[f][1][4 * g + 1] + acc[f][2][4 * g + 1]);
                     v[g].z = acc[f][0][4 * g + 2] + (acc[f][1][4 * g + 2] + acc[f][2][4 * g + 2]);
@@ -408,6 +421,12 @@ __global__ void __launch_bounds__(64 * WGM * WGN) __attribute__((amdgpu_waves_pe
                     if (f + 1 < MF) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) cnext[g] = *reinterpret_cast<const float4*>(cprev_b + eoff00[f + 1 < MF ? f + 1 : f] + coff + 8 * g);
+                    }
+                }
+                if constexpr (!PREF) {
+                    if (f == 0) {
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) cpre[BWD ? g : 0] = *reinterpret_cast<const float4*>(cprev_b + eoff + 8 * g);
                     }
                 }
                 if (f == 0) class_tail(v, eoff, 0, cpre);
@@ -437,7 +456,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) __attribute__((amdgpu_waves_pe
         constexpr bool last = (kc == NCH - 1 && t + 1 == kTapOrderD.start[cls + 1]);
         if constexpr (sidx + RING - 1 < NUNIT) loadB(bpf, sidx + RING - 1);
         if constexpr (sidx + 1 < NUNIT) loadA(an, sidx + 1);
-        if constexpr (BWD && first) {
+        if constexpr (BWD && first && PREF) {
             if (nsplit == 1) {
                 const int eoff = eoff00[0] + (py * d.WB + px) * Nn;
 #pragma unroll
@@ -452,16 +471,16 @@ __global__ void __launch_bounds__(64 * WGM * WGN) __attribute__((amdgpu_waves_pe
 #pragma unroll
             for (int f = 0; f < MF; ++f) acc[f][0] = mfma_bf16(bc.p[0][j], ac.p[0][f][j], (first && j == 0) ? z : acc[f][0]);
 #pragma unroll
-            for (int f = 0; f < MF; ++f) acc[f][1 % NACC] = mfma_bf16(bc.p[1][j], ac.p[0][f][j], (first && j == 0 && NACC == 3) ? z : acc[f][1 % NACC]);
+            for (int f = 0; f < MF; ++f) acc[f][C1] = mfma_bf16(bc.p[1][j], ac.p[0][f][j], (first && j == 0 && NACC > 1) ? z : acc[f][C1]);
 #pragma unroll
-            for (int f = 0; f < MF; ++f) acc[f][2 % NACC] = mfma_bf16(bc.p[0][j], ac.p[1][f][j], (first && j == 0 && NACC == 3) ? z : acc[f][2 % NACC]);
+            for (int f = 0; f < MF; ++f) acc[f][C2] = mfma_bf16(bc.p[0][j], ac.p[1][f][j], (first && j == 0 && NACC == 3) ? z : acc[f][C2]);
             if constexpr (NPL == 3) {      // bf16x6: + w2 a0, w0 a2, w1 a1
 #pragma unroll
-                for (int f = 0; f < MF; ++f) acc[f][1 % NACC] = mfma_bf16(bc.p[2][j], ac.p[0][f][j], acc[f][1 % NACC]);
+                for (int f = 0; f < MF; ++f) acc[f][C1] = mfma_bf16(bc.p[2][j], ac.p[0][f][j], acc[f][C1]);
 #pragma unroll
-                for (int f = 0; f < MF; ++f) acc[f][2 % NACC] = mfma_bf16(bc.p[0][j], ac.p[2][f][j], acc[f][2 % NACC]);
+                for (int f = 0; f < MF; ++f) acc[f][C2] = mfma_bf16(bc.p[0][j], ac.p[2][f][j], acc[f][C2]);
 #pragma unroll
-                for (int f = 0; f < MF; ++f) acc[f][1 % NACC] = mfma_bf16(bc.p[1][j], ac.p[1][f][j], acc[f][1 % NACC]);
+                for (int f = 0; f < MF; ++f) acc[f][C1] = mfma_bf16(bc.p[1][j], ac.p[1][f][j], acc[f][C1]);
             }
         }
         if constexpr (last) {
@@ -597,6 +616,11 @@ inline bool conv5_d16s_takes(const ConvGemmArgs& a) {
     if (a.ep.kind == UAD_EPI_BWD_ACT) return !xf;
     return xf;
 }
+// the fused final's training form on 16 x 16 tiles (the two-plane 8 x 16 instance with a 32-channel range asks; uad_op_conv_plan reports the answer)
+inline bool conv5_d16s_t16(const ConvGemmArgs& a) {
+    static const bool t16 = getenv("UAD_NO_D16S_T16") == nullptr;
+    return t16 && a.ep.fin_bits && a.nsplit == 1 && a.d.HS % 16 == 0;
+}
 template <int TH, int TW, int CST, int WGM, int WGN, int MF, int NPL>
 void launch_conv5_d16s_n(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
     if (a.ep.kind == UAD_EPI_BWD_ACT) launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_BWD_ACT, false, false, NPL>(a, grid, st);
@@ -605,8 +629,7 @@ void launch_conv5_d16s_n(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
             // round 6 (late): the training instance of the 32-channel last block on 16 x 16 tiles, two pixel fragments per wave -- half the workgroups, a weight
             // fragment feeds two MFMA chains, 27 % instead of 41 % halo overhead in the staged tile: dec3.fwd 67.8 -> 62.2 us same box.  UAD_NO_D16S_T16: 8 x 16.
             if constexpr (TH == 8 && TW == 16 && CST == 32 && WGM == 4 && MF == 1 && NPL == 2) {
-                static const bool t16 = getenv("UAD_NO_D16S_T16") == nullptr;
-                if (t16 && a.ep.fin_bits && a.nsplit == 1 && a.d.HS % 16 == 0) {
+                if (conv5_d16s_t16(a)) {
                     grid.x = (a.d.HS / 16) * (a.d.WS / 16);
                     launch_conv5_d16s_e<16, 16, 32, 4, 1, 2, UAD_EPI_FINAL, true, true, 2>(a, grid, st);
                     return;

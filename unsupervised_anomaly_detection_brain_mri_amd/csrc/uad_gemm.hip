@@ -1697,6 +1697,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) __attribute__((amdgpu_waves_pe
 // crosses the boundary as an untyped pointer (anonymous-namespace types are unit-local).
 }  // namespace
 bool uad_d16s_takes_v(const void* conv_gemm_args);
+bool uad_d16s_t16_v(const void* conv_gemm_args, int bn, int cst, int npl);
 void uad_d16s_launch_v2(const void* conv_gemm_args, unsigned gx, unsigned gy, unsigned gz, int bn, int cst, bool any_order, hipStream_t st);      // uad_gemm_d16s.hip: two planes
 void uad_d16s_launch_v3(const void* conv_gemm_args, unsigned gx, unsigned gy, unsigned gz, int bn, int cst, bool any_order, hipStream_t st);      // uad_gemm_d16s3.hip: three
 namespace {
@@ -2784,6 +2785,10 @@ bool x6_route(const UadConvDesc& d, bool f_type, const GemmPlan& p) {
     const int cst = (d.CS % p.nsplit == 0) ? d.CS / p.nsplit : 0;
     return p.sc.BN == 64 ? (cst == 32 || cst == 64 || cst == 128) : (cst == 32 || cst == 64);
 }
+// the fused final epilogue: which plans the kernels on bf16 planes (conv5_d16 / conv5_d16s: whole channel range of 32 or 64 in one 32-column workgroup) and the
+// exact-fp32 instance conv5_d_kernel<8,16,32,4,1,true> take.  One predicate each for uad_conv_d_can_fuse_final*, run_plan and uad_conv_d_kernel_query.
+inline bool final_plan_ok16(const GemmPlan& p, const UadConvDesc& d) { return p.path == PATH_SPATIAL && p.nsplit == 1 && p.sc.BN == 32 && d.CB == 32 && (d.CS == 32 || d.CS == 64); }
+inline bool final_plan_ok32(const GemmPlan& p, int Nn) { return p.path == PATH_SPATIAL && p.nsplit == 1 && p.sc.BN != 64 && p.sc.CK == 32 && Nn == 32; }
 // inst_ok: the launch's epilogue / activation-on-load form has a three-plane instance (D kind: d_x6_form_ok; every F form has one).  *x6: the route taken.
 GemmPlan plan_for(const UadConvDesc& d, bool f_type, bool have_pack, size_t ws_floats, int ncounters, int planes16, bool inst_ok = true, bool* x6 = nullptr) {
     GemmPlan p = plan_gemm(d, f_type, have_pack, ws_floats, ncounters);
@@ -2797,6 +2802,7 @@ inline bool d_x6_form_ok(const UadEpilogue& ep, bool has_xf) {
     return ep.kind == UAD_EPI_FINAL ? (ep.fin_dc == nullptr && ep.ealpha >= 0.f && ep.ealpha <= 1.f && has_xf) : ep.kind == UAD_EPI_BWD_ACT ? !has_xf : has_xf;
 }
 }  // namespace
+bool uad_conv_d_x6_form_ok(const UadEpilogue& ep, bool has_xf) { return d_x6_form_ok(ep, has_xf); }
 bool uad_conv_x6_takes(const UadConvDesc& d, bool f_type, size_t ws_floats, int ncounters) { return x6_route(d, f_type, plan_gemm(d, f_type, true, ws_floats, ncounters)); }
 int uad_conv_f_tiles(const UadConvDesc& d, bool have_pack, size_t ws_floats, int ncounters, int planes16) { return plan_for(d, true, have_pack, ws_floats, ncounters, planes16).tiles; }
 int uad_conv_d_tiles(const UadConvDesc& d, bool have_pack, size_t ws_floats, int ncounters, int planes16) { return plan_for(d, false, have_pack, ws_floats, ncounters, planes16).tiles; }
@@ -2809,13 +2815,13 @@ bool uad_conv_d_can_fuse_final(const UadConvDesc& d, bool have_pack16, size_t ws
     if (!have_pack16 || getenv("UAD_NO_FUSED_FINAL")) return false;
     const GemmPlan p = plan_gemm(d, false, true, ws_floats);
     // conv5_d16_kernel<8,16,CST,4,1> with the whole channel range in one workgroup column block
-    return p.path == PATH_SPATIAL && p.nsplit == 1 && p.sc.BN == 32 && d.CB == 32 && (d.CS == 32 || d.CS == 64);
+    return final_plan_ok16(p, d);
 }
 // exact-fp32 mode: conv5_d_kernel<8,16,32,4,1,FIN> (UAD_NO_FUSED_FINAL_F32=1: the separate final_kernel pass)
 bool uad_conv_d_can_fuse_final_f32(const UadConvDesc& d, bool have_pack, size_t ws_floats) {
     if (!have_pack || getenv("UAD_NO_FUSED_FINAL") || getenv("UAD_NO_FUSED_FINAL_F32")) return false;
     const GemmPlan p = plan_gemm(d, false, true, ws_floats);
-    return p.path == PATH_SPATIAL && p.nsplit == 1 && p.sc.TH == 8 && p.sc.TW == 16 && p.sc.BN == 32 && p.sc.CK == 32 && d.CB == 32;
+    return final_plan_ok32(p, d.CB);
 }
 size_t uad_conv_ws_floats(const UadConvDesc& d, bool f_type, bool have_pack) { return plan_gemm(d, f_type, have_pack, (size_t)1 << 40).ws_floats; }
 // tests (uad_debug_plan): what uad_launch_conv_f / _d would run, from the launchers' own decision functions.  out[10]:
@@ -2858,14 +2864,29 @@ void uad_launch_pack_weights_bf16_3p(const float* params, unsigned short* w3_f, 
 }
 
 namespace {
+// the split fields of a spatial launch's arguments, as the kernel selection below reads them (a.Out still the caller's output on entry)
+inline void spatial_split_args(const GemmPlan& p, ConvGemmArgs& a, float* ws) {
+    float* out = a.Out;
+    a.nsplit = 1;
+    if (p.nsplit > 1) { a.Out = ws; a.nsplit = p.nsplit; a.out_final = out; }
+    if (!(p.nsplit > 1 && p.inkernel && a.Wp16)) a.sk_counter = nullptr;
+}
+// D kind of a spatial launch on bf16 planes: the kernel generation that runs and the channel range `cst` a workgroup stages (0: CA does not divide by the splits).
+// One decision for run_plan and uad_conv_d_kernel_query; `a` after spatial_split_args.
+inline bool d16_instance(int bn, int cst) { return bn == 64 ? (cst == 128 || cst == 64 || cst == 32) : (cst == 64 || cst == 32); }
+inline int d16_generation(const GemmPlan& p, const ConvGemmArgs& a, int* cst_out) {
+    const int cst = (a.CA % p.nsplit == 0) ? a.CA / p.nsplit : 0;
+    *cst_out = cst;
+    if (!d16_instance(p.sc.BN, cst)) return UAD_DGEN_BF16_D;        // conv5_bf16_kernel<KIND_D>: channel chunks streamed through LDS
+    return conv5_d16s_takes(a) ? UAD_DGEN_LANE_PIXEL : UAD_DGEN_CLASS_SEQ;      // uad_conv16s.inc | conv5_d16_kernel (its fallback)
+}
 void run_plan(const GemmPlan& p, ConvGemmArgs& a, bool f_type, float* ws, hipStream_t st) {
     const UadConvDesc& d = a.d;
     a.nsplit = 1; a.out_elems = p.out_elems;
     a.dbg = 0; a.dbgbuf = nullptr;
     if (p.path == PATH_SPATIAL) {
         float* out = a.Out;
-        if (p.nsplit > 1) { a.Out = ws; a.nsplit = p.nsplit; a.out_final = out; }
-        if (!(p.nsplit > 1 && p.inkernel && a.Wp16)) a.sk_counter = nullptr;
+        spatial_split_args(p, a, ws);
         dim3 grid((d.HS / p.sc.TH) * (d.WS / p.sc.TW), d.N, (a.Nn / p.sc.BN) * p.nsplit);
         if (a.Wp16) {   // bf16x3 math mode
             if (f_type) {
@@ -2879,10 +2900,10 @@ void run_plan(const GemmPlan& p, ConvGemmArgs& a, bool f_type, float* ws, hipStr
                 else launch_conv5_f16<8, 16, 16, 4, 1>(a, grid, st);
             } else {
                 // class-sequential kernel whenever the workgroup's whole channel range fits in LDS (CA == cst * nsplit)
-                const int cst = (a.CA % p.nsplit == 0) ? a.CA / p.nsplit : 0;
-                constexpr bool seq = true;      // class-sequential generation (conv5_d16_kernel): the fallback of the lane = pixel one
-                const bool lp = seq && conv5_d16s_takes(a);      // lane = pixel generation (uad_conv16s.inc)
-                if (lp && ((p.sc.BN == 64 && (cst == 128 || cst == 64 || cst == 32)) || (p.sc.BN == 32 && (cst == 64 || cst == 32)))) launch_conv5_d16s_any(a, grid, p.sc.BN, cst, st);
+                int cst = 0;
+                const int gen = d16_generation(p, a, &cst);
+                const bool seq = gen == UAD_DGEN_CLASS_SEQ;      // class-sequential generation (conv5_d16_kernel): the fallback of the lane = pixel one
+                if (gen == UAD_DGEN_LANE_PIXEL) launch_conv5_d16s_any(a, grid, p.sc.BN, cst, st);      // lane = pixel generation (uad_conv16s.inc)
                 else if (a.npl == 3) { fprintf(stderr, "uad: a bf16x6 launch reached a kernel without the three-plane form (x6_route decides before run_plan)\n"); abort(); }
                 else
                 if (p.sc.BN == 64) {
@@ -2900,7 +2921,7 @@ void run_plan(const GemmPlan& p, ConvGemmArgs& a, bool f_type, float* ws, hipStr
             else UAD_SPATIAL_LAUNCH((conv5_f_kernel<8, 16, 16, 4, 1>), grid, dim3(256), 0, st, a);
         } else {
             if (p.sc.BN == 64 && a.ep.kind != UAD_EPI_FINAL) UAD_SPATIAL_LAUNCH((conv5_d_kernel<8, 8, 32, 2, 2>), grid, dim3(256), 0, st, a);
-            else if (p.sc.CK == 32 && a.ep.kind == UAD_EPI_FINAL && p.nsplit == 1 && a.Nn == 32) UAD_SPATIAL_LAUNCH((conv5_d_kernel<8, 16, 32, 4, 1, true>), grid, dim3(256), 0, st, a);
+            else if (a.ep.kind == UAD_EPI_FINAL && final_plan_ok32(p, a.Nn)) UAD_SPATIAL_LAUNCH((conv5_d_kernel<8, 16, 32, 4, 1, true>), grid, dim3(256), 0, st, a);
             else if (a.ep.kind == UAD_EPI_FINAL) { fprintf(stderr, "uad: fused final epilogue asked of an exact-fp32 launch that cannot run it (check uad_conv_d_can_fuse_final_f32 first)\n"); abort(); }
             else if (p.sc.CK == 32) UAD_SPATIAL_LAUNCH((conv5_d_kernel<8, 16, 32, 4, 1>), grid, dim3(256), 0, st, a);
             else UAD_SPATIAL_LAUNCH((conv5_d_kernel<8, 16, 16, 4, 1>), grid, dim3(256), 0, st, a);
@@ -2962,6 +2983,26 @@ void uad_launch_conv_f(const UadConvDesc& d, const float* big_in, UadXform xf, c
     run_plan(p, a, true, ws.ptr, st);
 }
 
+namespace {
+// What uad_launch_conv_d settles between filling the arguments and run_plan: the plan, the three-plane route (or the exact-fp32 one in its place) and the arrival
+// counters.  *no_pack: a bf16x6 launch outside the three-plane kernels found no fp32 pack (the launcher aborts).  Shared with uad_conv_d_kernel_query.
+GemmPlan settle_conv_d(ConvGemmArgs& a, const UadGemmWs& ws, int planes16, bool* x6, bool* no_pack) {
+    const UadConvDesc& d = a.d;
+    const GemmPlan p = plan_for(d, false, a.Wp != nullptr || a.Wp16 != nullptr, ws.ptr ? ws.floats : 0, (a.Wp16 && ws.counters) ? ws.ncounters : 0, planes16,
+                                d_x6_form_ok(a.ep, a.xf.scale != nullptr), x6);
+    *no_pack = false;
+    if (planes16 == 3) {
+        if (*x6) a.npl = 3;
+        else {
+            if (!a.Wp && d.KS == 5) *no_pack = true;
+            a.Wp16 = nullptr;
+        }
+    }
+    if (p.inkernel) a.sk_counter = ws.counters;
+    return p;
+}
+}  // namespace
+
 void uad_launch_conv_d(const UadConvDesc& d, const float* small_in, UadXform xf, const float* W, float* big_out,
                        UadEpilogue ep, hipStream_t st, const float* Wpacked, UadGemmWs ws, const unsigned short* Wp16,
                        long long w16_plane, bool generic_bf16x3, int planes16) {
@@ -2972,18 +3013,38 @@ void uad_launch_conv_d(const UadConvDesc& d, const float* small_in, UadXform xf,
     a.M = d.N * d.HS * d.WS; a.CA = d.CS; a.Nn = d.CB;
     a.lws = ilog2_exact(d.WS); a.lhs = ilog2_exact(d.HS); a.dbgbuf = nullptr;
     a.sk_counter = nullptr; a.out_final = nullptr;
-    bool x6 = false;
-    const GemmPlan p = plan_for(d, false, Wpacked != nullptr || Wp16 != nullptr, ws.ptr ? ws.floats : 0, (Wp16 && ws.counters) ? ws.ncounters : 0, planes16,
-                                d_x6_form_ok(ep, xf.scale != nullptr), &x6);
-    if (planes16 == 3) {
-        if (x6) a.npl = 3;
-        else {
-            if (!Wpacked && d.KS == 5) { fprintf(stderr, "uad: a bf16x6 launch outside the three-plane spatial kernels needs the fp32 pack (uad_conv_x6_takes / uad_conv_k3_takes)\n"); abort(); }
-            a.Wp16 = nullptr;
-        }
-    }
-    if (p.inkernel) a.sk_counter = ws.counters;
+    bool x6 = false, no_pack = false;
+    const GemmPlan p = settle_conv_d(a, ws, planes16, &x6, &no_pack);
+    if (no_pack) { fprintf(stderr, "uad: a bf16x6 launch outside the three-plane spatial kernels needs the fp32 pack (uad_conv_x6_takes / uad_conv_k3_takes)\n"); abort(); }
     run_plan(p, a, false, ws.ptr, st);
+}
+
+// tests (uad_op_conv_plan): the kernel a D-kind launch with these operands would run, answered by the launcher's own code (settle_conv_d, spatial_split_args,
+// d16_generation); nothing is launched and no pointer is read.  out3: 0 generation (UAD_DGEN_*; 0: not a spatial launch), 1 channel range per workgroup `cst`
+// (bf16 planes only), 2 the launch would abort() (bf16x6 without the fp32 pack it needs, or a fused final epilogue the kernel that runs does not have), 3 the fused
+// final's tile height (16 | 8; 0: another epilogue)
+void uad_conv_d_kernel_query(const UadConvDesc& d, bool has_xf, const UadEpilogue& ep, bool have_pack32, bool have_pack16, UadGemmWs ws, int planes16, long long* out3) {
+    static float some;      // stands for every operand that is only tested for presence
+    ConvGemmArgs a;
+    a.Wp = have_pack32 ? &some : nullptr; a.Wp16 = have_pack16 ? reinterpret_cast<const unsigned short*>(&some) : nullptr; a.npl = 2;
+    a.ep = ep; a.d = d; a.xf = UadXform(); a.xf.scale = has_xf ? &some : nullptr; a.Out = &some;
+    a.M = d.N * d.HS * d.WS; a.CA = d.CS; a.Nn = d.CB;
+    a.sk_counter = nullptr; a.out_final = nullptr;
+    bool x6 = false, no_pack = false;
+    const GemmPlan p = settle_conv_d(a, ws, planes16, &x6, &no_pack);
+    out3[0] = 0; out3[1] = 0; out3[2] = no_pack ? 1 : 0; out3[3] = 0;
+    if (p.path != PATH_SPATIAL) return;
+    spatial_split_args(p, a, &some);
+    if (a.Wp16) {
+        int cst = 0;
+        out3[0] = d16_generation(p, a, &cst); out3[1] = cst;
+        out3[3] = ep.kind != UAD_EPI_FINAL ? 0 : (out3[0] == UAD_DGEN_LANE_PIXEL && uad_d16s_t16_v(&a, p.sc.BN, cst, a.npl)) ? 16 : 8;
+        if (out3[0] != UAD_DGEN_LANE_PIXEL && a.npl == 3) out3[2] = 1;
+        if (ep.kind == UAD_EPI_FINAL && !final_plan_ok16(p, d)) out3[2] = 1;
+    } else {
+        out3[0] = UAD_DGEN_F32; out3[3] = ep.kind == UAD_EPI_FINAL ? 8 : 0;
+        if (ep.kind == UAD_EPI_FINAL && !final_plan_ok32(p, a.Nn)) out3[2] = 1;
+    }
 }
 
 // ---- W-type host side -------------------------------------------------------------------------

@@ -4,3 +4,8 @@
 #include "uad_gemm_d16s_body.inc"
 
 bool uad_d16s_takes_v(const void* conv_gemm_args) { return conv5_d16s_takes(*static_cast<const ConvGemmArgs*>(conv_gemm_args)); }
+// the instance list of launch_conv5_d16s_n: a fused final in its training form runs on 16 x 16 tiles
+bool uad_d16s_t16_v(const void* conv_gemm_args, int bn, int cst, int npl) {
+    const ConvGemmArgs& a = *static_cast<const ConvGemmArgs*>(conv_gemm_args);
+    return a.ep.kind == UAD_EPI_FINAL && bn == 32 && cst == 32 && npl == 2 && conv5_d16s_t16(a);
+}

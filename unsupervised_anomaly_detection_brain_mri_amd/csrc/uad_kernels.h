@@ -125,6 +125,15 @@ int uad_conv_d_tiles(const UadConvDesc& d, bool have_pack = true, size_t ws_floa
 size_t uad_conv_ws_floats(const UadConvDesc& d, bool f_type, bool have_pack);
 // tests (uad_debug_plan): the launch plan of uad_launch_conv_f / _d / _w as ten integers (fields: uad_gemm.hip, include/uad_hip.h)
 void uad_conv_plan_query(const UadConvDesc& d, bool f_type, bool have_pack, size_t ws_floats, int ncounters, int planes16, bool inst_ok, long long* out);      // inst_ok: D kind, the epilogue form has a three-plane instance
+// ... and the kernel generation of a D-kind k5 s2 spatial launch with these operands (uad_gemm.hip: run_plan).  out3: 0 generation (0: no spatial launch), 1 channel
+// range a workgroup stages (`cst`; bf16 planes only), 2 the launch would abort(), 3 tile height of a fused final (16 | 8; 0: another epilogue)
+enum { UAD_DGEN_LANE_PIXEL = 1,      // conv5_d16s_kernel (uad_conv16s.inc), two or three planes
+       UAD_DGEN_CLASS_SEQ = 2,       // conv5_d16_kernel: whole channel range in LDS, parity classes in sequence
+       UAD_DGEN_BF16_D = 3,          // conv5_bf16_kernel<KIND_D>: `cst` outside the instance list
+       UAD_DGEN_F32 = 4 };           // conv5_d_kernel on the fp32 pack
+void uad_conv_d_kernel_query(const UadConvDesc& d, bool has_xf, const UadEpilogue& ep, bool have_pack32, bool have_pack16, UadGemmWs ws, int planes16, long long* out4);
+// inst_ok of uad_conv_plan_query for a D-kind launch: its epilogue / activation-on-load form has a three-plane instance
+bool uad_conv_d_x6_form_ok(const UadEpilogue& ep, bool has_xf);
 void uad_conv_w_plan_query(const UadConvDesc& d, bool math_bf16x3, int planes16, bool fbb, bool xa, bool xs, bool generic_bf16x3, bool defer_reduce, long long* out);
 // W-type: dW[tap][cb][cs] = sum_{n,i,j} xfb(big)[..tap..,cb] * xfs(small)[n,i,j,cs]
 // `partial` must hold uad_conv_w_partial_floats(d) floats.
