@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, 'libuad_hip.so')
-SOURCES = ['uad_gemm.hip', 'uad_gemm_d16s.hip', 'uad_gemm_d16s3.hip', 'uad_misc.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_hist.hip', 'uad_flow.hip', 'uad_resize.hip', 'uad_cc.hip', 'uad_crops.hip', 'uad_batch.hip', 'uad_render.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_allreduce.hip']
+SOURCES = ['uad_gemm.hip', 'uad_gemm_d16s.hip', 'uad_gemm_d16s3.hip', 'uad_misc.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_hist.hip', 'uad_flow.hip', 'uad_resize.hip', 'uad_cc.hip', 'uad_crops.hip', 'uad_batch.hip', 'uad_render.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_ops.hip', 'uad_allreduce.hip']
 ARCH = 'gfx950'
 # per-file flags.  uad_flow.hip must return the bits of utils/curvature_flow.py, uad_resize.hip those of utils/resize.py and uad_render.hip those of
 # utils/render.py: no multiply-add may be fused, in host or device code; uad_hist.hip's centred squares are added as tests/native/hist_emu.cpp adds them;
@@ -39,7 +39,7 @@ def build(force=False, verbose=False):
     hipcc = _hipcc()
     objdir = os.path.join(ROOT, 'build', 'uad_hip')
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, 'uad_kernels.h'), os.path.join(CSRC, 'uad_allreduce.h'), os.path.join(ROOT, 'include', 'uad_hip.h'), os.path.join(CSRC, 'uad_gan_kernels.inc'),
+    headers = [os.path.join(CSRC, 'uad_kernels.h'), os.path.join(CSRC, 'uad_handle.h'), os.path.join(CSRC, 'uad_allreduce.h'), os.path.join(ROOT, 'include', 'uad_hip.h'), os.path.join(CSRC, 'uad_gan_kernels.inc'),
                os.path.join(CSRC, 'uad_gan_create.inc'), os.path.join(CSRC, 'uad_conv16s.inc'), os.path.join(CSRC, 'uad_convk16.inc'),
                os.path.join(CSRC, 'uad_conv5_f32.inc'), os.path.join(CSRC, 'uad_conv5_f32w.inc'), os.path.join(CSRC, 'uad_gemm_common.h'), os.path.join(CSRC, 'uad_gemm_d16s_body.inc')]      # the .inc files are textual parts of uad_gan.hip
     objs = []

@@ -18,15 +18,9 @@ typedef enum { ncclSum = 0, ncclProd = 1, ncclMax = 2, ncclMin = 3, ncclAvg = 4 
 #endif
 #include "../../include/uad_hip.h"
 #include "uad_allreduce.h"
+#include "uad_kernels.h"      // uad_fail, HIP_TRY
 
-int uad_fail(int code, const char* fmt, ...);
 #define fail uad_fail
-
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 // RCCL is bound at run time: librccl.so.1 as the process already has it (the copy PyTorch-ROCm loads), else from the loader path.  libuad_hip.so
 // itself has no link-time dependency on it -- single-GPU users and the CPU-side symbol tests never touch it.

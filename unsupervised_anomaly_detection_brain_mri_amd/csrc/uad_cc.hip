@@ -21,12 +21,6 @@
 
 #define fail uad_fail
 
-#define CC_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
 
 constexpr int CC_TX = 32, CC_TY = 8, CC_TZ = 4, CC_TILE = CC_TX * CC_TY * CC_TZ, CC_THREADS = 256;
@@ -215,9 +209,9 @@ int uad_cc_label(const float* vol, int D, int H, int W, int slab, int* labels, i
     if (!vol || !labels) return fail(UAD_ERR_INVALID, "cc_label: bad arguments");
     if (const int rc = check_shape("cc_label", D, H, W)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (n_components) CC_TRY(hipMemsetAsync(n_components, 0, sizeof(int), st));
+    if (n_components) HIP_TRY(hipMemsetAsync(n_components, 0, sizeof(int), st));
     launch_label(vol, nullptr, D, H, W, slab, labels, n_components, st);
-    CC_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
@@ -228,7 +222,7 @@ int uad_detection_rate(const float* pred, const float* gt, int D, int H, int W, 
     const size_t total = (size_t)D * H * W;
     const unsigned nb = (unsigned)((total + 255) / 256);
     int* ws = nullptr;                           // Li | Lp | Lg | psz
-    CC_TRY(hipMalloc((void**)&ws, 4 * total * sizeof(int)));
+    HIP_TRY(hipMalloc((void**)&ws, 4 * total * sizeof(int)));
     int *Li = ws, *Lp = ws + total, *Lg = ws + 2 * total, *psz = ws + 3 * total;
     hipError_t e = hipMemsetAsync(psz, 0, total * sizeof(int), st);
     if (e == hipSuccess) e = hipMemsetAsync(counts3, 0, 3 * sizeof(long long), st);

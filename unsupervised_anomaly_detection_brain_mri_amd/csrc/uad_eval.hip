@@ -14,12 +14,6 @@
 
 #define fail uad_fail
 
-#define EV_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
 
 // ------------------------------------------------------------------------------------------------
@@ -427,7 +421,7 @@ int uad_erode_cross(const float* mask, int n, int H, int W, int iterations, floa
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(erode_cross_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     hipLaunchKernelGGL(erode_cross_kernel, dim3(n), dim3(1024), lds, (hipStream_t)stream, mask, H, W, iterations, out);
-    EV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
@@ -437,14 +431,14 @@ int uad_median3d(const float* vol, int D, int H, int W, int ksize, float* out, v
     if (vol == out) return fail(UAD_ERR_INVALID, "median3d: in-place is not supported");
     dim3 grid((W + 7) / 8, (H + 7) / 8, (D + 7) / 8);
     hipLaunchKernelGGL(median5_kernel, grid, dim3(512), 0, (hipStream_t)stream, vol, D, H, W, out);
-    EV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
 int uad_mc_stats(const float* recs, const float* mask, int K, long long total, float* mean, float* var, void* stream) {
     if (!recs || !mean || K <= 0 || total <= 0) return fail(UAD_ERR_INVALID, "mc_stats: bad arguments");
     hipLaunchKernelGGL(mc_stats_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, recs, mask, K, (size_t)total, mean, var);
-    EV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
@@ -455,7 +449,7 @@ int uad_cc_filter(const float* vol, int D, int H, int W, int max_voxels, float* 
     const size_t total = (size_t)D * H * W;
     if (total > 0x7fffffffULL) return fail(UAD_ERR_UNSUPPORTED, "cc_filter: volume too large");
     hipLaunchKernelGGL(cc_filter_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, vol, D, H, W, max_voxels, out);
-    EV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
@@ -473,7 +467,7 @@ int uad_scores_create(const float* pred, const float* label, long long n, uad_sc
     int rc = UAD_OK;
     auto cleanup = [&]() { hipFree(key_a); hipFree(key_b); hipFree(counts); hipFree(pos); hipFree(didx); hipFree(d_nd); hipFree(bsum32); hipFree(lab_a); hipFree(lab_b);
                            hipFree(flag); hipFree(bsum64); hipFree(d_res); };
-#define EV_TRY2(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); cleanup(); uad_scores_destroy(s); return rc; } } while (0)
+#define EV_TRY2(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(UAD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); cleanup(); uad_scores_destroy(s); return rc; } } while (0)
     const size_t N = (size_t)n;
     const unsigned blocks = (unsigned)((N + 255) / 256);
     const unsigned ntiles = (unsigned)((N + RS_TILE - 1) / RS_TILE);
@@ -543,10 +537,10 @@ int uad_scores_dice(uad_scores_t* s, const double* thresholds, int k, double* di
     hipStream_t st = (hipStream_t)stream;
     for (int o = 0; o < k; o += s->cap) {
         const int c = (k - o < s->cap) ? k - o : s->cap;
-        EV_TRY(hipMemcpyAsync(s->dthr, thresholds + o, c * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->dthr, thresholds + o, c * sizeof(double), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(dice_at_kernel, dim3(1), dim3(64), 0, st, s->score, s->tp, s->n, s->dthr, c, s->dout);
-        EV_TRY(hipMemcpyAsync(dice + o, s->dout, c * sizeof(double), hipMemcpyDeviceToHost, st));
-        EV_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemcpyAsync(dice + o, s->dout, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return UAD_OK;
 }
@@ -555,18 +549,18 @@ int uad_scores_threshold_at_precision(const uad_scores_t* s, double precision, d
     if (!s || !threshold || !(precision >= 0.0)) return fail(UAD_ERR_INVALID, "scores_threshold_at_precision: bad arguments");
     hipStream_t st = s->stream;
     unsigned* d_best = (unsigned*)s->dout;       // (the handle's threshold-batch scratch; a handle is not thread-safe)
-    EV_TRY(hipMemsetAsync(d_best, 0, sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(d_best, 0, sizeof(unsigned), st));
     const unsigned long long nblk = (s->n + 255) / 256;
     hipLaunchKernelGGL(prec_threshold_kernel, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(256), 0, st, (const float*)s->score,
                        (const unsigned long long*)s->tp, s->n, precision, d_best);
-    EV_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     unsigned best = 0;
-    EV_TRY(hipMemcpyAsync(&best, d_best, sizeof best, hipMemcpyDeviceToHost, st));
-    EV_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&best, d_best, sizeof best, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     // no point qualifies: numpy's argmax of an all-False array is 0, the smallest threshold
     float v = 0.f;
-    EV_TRY(hipMemcpyAsync(&v, s->score + (best ? best - 1 : s->n - 1), sizeof v, hipMemcpyDeviceToHost, st));
-    EV_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(&v, s->score + (best ? best - 1 : s->n - 1), sizeof v, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     *threshold = (double)v;
     return UAD_OK;
 }

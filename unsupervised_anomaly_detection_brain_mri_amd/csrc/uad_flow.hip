@@ -130,17 +130,11 @@ inline dim3 flow_block() { return dim3(FLOW_TX, FLOW_TY); }
 #if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 #define fail uad_fail
 
-#define FLOW_TRY(expr)                                                                            \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
 template <class T>
 int flow_sweep(const T* src, int nz, int ny, int nx, const FlowScale& sc, double* dst, hipStream_t st) {
     hipLaunchKernelGGL(flow_sweep_kernel<T>, flow_grid(nz, ny, nx), flow_block(), 0, st, src, nz, ny, nx, sc, dst);
-    FLOW_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 }  // namespace
@@ -172,7 +166,7 @@ int uad_curvature_flow(const void* in, int in_is_f32, int nz, int ny, int nx, co
         const unsigned blocks = (unsigned)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536);
         if (in_is_f32) hipLaunchKernelGGL(flow_copy_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)in, count, out);
         else hipLaunchKernelGGL(flow_copy_kernel<double>, dim3(blocks), dim3(256), 0, st, (const double*)in, count, out);
-        FLOW_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         return UAD_OK;
     }
     FlowScale sc;

@@ -1,7 +1,8 @@
 // f-AnoGAN (unified graph) on gfx950: LayerNorm-HW kernels (forward, backward, and the second-order backward the WGAN-GP
 // penalty needs), the small heads / losses, and the orchestration of the three optimisation phases behind the C-ABI
 // (include/uad_hip.h, uad_gan_*).  The k5 s2 convolutions, their data and filter gradients, the dense layers and Adam are
-// the kernels of uad_gemm.hip / uad_misc.hip.
+// the kernels of uad_gemm.hip / uad_misc.hip.  The handle's tensor table, flat buffers and packs are the UadHandleCore of uad_handle.h,
+// shared with the AE / VAE-family handle (uad_model.hip).
 //
 // Graph restated (reference): models/fanogan.py:11-84, models/customlayers.py:16-38 (use_batchnorm=False branches),
 // losses / optimisers trainers/fAnoGAN.py:50-77, reconstruct :220-239.
@@ -21,34 +22,15 @@
 #include <string>
 #include <vector>
 
-#include "../../include/uad_hip.h"
-#include "uad_allreduce.h"
-#include "uad_kernels.h"
-
-#define fail uad_fail
+#include "uad_handle.h"
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-constexpr float kBnEps = 1e-3f;     // tf.layers.BatchNormalization default epsilon (encoder, frozen statistics)
 constexpr float kLnEps = 1e-3f;     // keras LayerNormalization default epsilon
-constexpr float kLrelu = 0.3f;      // keras LeakyReLU() default
 
 #include "uad_gan_kernels.inc"
 
 // ================================================================================================ handle
-struct Tensor {
-    std::string name;
-    long long off;
-    int rank;
-    int shape[4];
-    long long count() const { return (long long)shape[0] * shape[1] * shape[2] * shape[3]; }
-};
 struct Block {            // conv / convT followed by a norm + (Leaky)ReLU
     UadConvDesc d;        // geometry at batch 1
     long long w, b, gamma, beta;
@@ -57,29 +39,22 @@ struct Block {            // conv / convT followed by a norm + (Leaky)ReLU
 
 }  // namespace
 
-struct uad_gan {
+// UadHandleCore: the tensor table, the flat buffers, the packs (wpack3_*: ResNet graph only -- THREE bf16 planes of the k3 kernels for the bf16x6 products of
+// the exact passes; null: fp32 kernels), the GEMM workspace, the all-reduce lane, the named allocations uad_gan_debug_buffer looks up
+struct uad_gan : UadHandleCore {
     uad_gan_config_t cfg;
     int npool, cenc, cmid, flat;
-    std::vector<Tensor> tensors;
-    long long nparams;
     long long grp_off[3], grp_cnt[3], step[3];
-    float *params, *grads, *adam_m, *adam_v;
     float *adam_m2, *adam_v2;          // AnoVAE-GAN: the Generator's slots inside optim_vae (its optim_gen slots are adam_m / adam_v)
-    float *wpack_f, *wpack_d, *wpack16_f, *wpack16_d;
     float* ln_xch = nullptr; unsigned* ln_flags = nullptr; size_t ln_xcap = 0; unsigned ln_epoch = 0;     // exchange scratch of the clustered LayerNorm kernels (grown on first use)
-    float *wpack3_f, *wpack3_d;        // ResNet graph: THREE bf16 planes of the k3 kernels (bf16x6 products of the exact passes), 4 * nparams ushorts each; null: fp32 kernels
-    int math;
-    bool packed_valid;
     // library-issued, bucketed gradient all-reduce of a phase's trained group (uad_gan_allreduce_attach, round 6): the group's tensors are cut into up to four
     // contiguous buckets of the lane; a bucket's collective is enqueued on the lane's stream as soon as the LAST kernel that writes one of its tensors is
     // enqueued (gan_grad_final marks a tensor; the pending count of its bucket reaching zero issues it), i.e. while the backward of the earlier layers still runs
-    UadArLane ar;
     struct ArBucket { int pending; bool issued; } ar_b[4];
     bool ar_active; hipStream_t ar_st; int ar_err;      // ar_err: the phase's first failed issue (later buckets are not issued)
     std::vector<std::pair<long long, int>> ar_tb;      // (tensor offset, bucket) of the trained group's tensors, and whether it was marked
     std::vector<char> ar_marked;
     bool pack_all; long long dirty_lo, dirty_hi;      // which parameters changed since the last pack: everything, or [dirty_lo, dirty_hi) (an optimizer step touches ONE group)
-    UadGemmWs ws;
     std::vector<Block> E, G, D;
     long long e_cw, e_cb, e_dw, e_db;                   // Encoder/conv2d, Encoder/dense
     long long e_sw, e_sb;                               // AnoVAE-GAN: Encoder/dense_1 (log-sigma head; Encoder/dense is mu)
@@ -154,14 +129,9 @@ struct uad_gan {
     float *s_hf, *s_stf;                             // relu(LN(last generator block)) + statistics
     float *s_out0, *s_dout0;                         // critic first conv output [4n] and its gradient [4n]
     float *s_ta, *s_tb, *s_sp, *s_sct;               // temporaries: conv2 / conv1 data gradients, pooled shortcut, shortcut conv output
-    std::map<std::string, std::pair<float*, long long>> dbg;
-    std::vector<void*> allocs;
 };
 
 namespace {
-
-float* P(uad_gan* m, long long off) { return m->params + off; }
-float* Gr(uad_gan* m, long long off) { return m->grads + off; }
 
 // ---- bucketed all-reduce of the trained group's gradients (data parallelism, library-issued RCCL) --------------------------------------------
 static void gan_ar_issue(uad_gan* m, int b) {
@@ -175,14 +145,14 @@ static void gan_ar_issue(uad_gan* m, int b) {
 static void gan_ar_begin(uad_gan* m, long long off, long long cnt, hipStream_t st) {
     m->ar_active = false;
     if (!m->ar.comm || cnt <= 0) return;
-    std::vector<const Tensor*> ts;
-    for (const Tensor& t : m->tensors) if (t.off >= off && t.off + t.count() <= off + cnt) ts.push_back(&t);
-    std::sort(ts.begin(), ts.end(), [](const Tensor* a, const Tensor* b) { return a->off < b->off; });
+    std::vector<const UadTensor*> ts;
+    for (const UadTensor& t : m->tensors) if (t.off >= off && t.off + t.count() <= off + cnt) ts.push_back(&t);
+    std::sort(ts.begin(), ts.end(), [](const UadTensor* a, const UadTensor* b) { return a->off < b->off; });
     constexpr int K = 4;
     m->ar.nb = K; m->ar_tb.clear(); m->ar_marked.assign(ts.size(), 0);
     for (int b = 0; b < K; ++b) { m->ar_b[b] = {0, false}; m->ar.off[b] = m->ar.cnt[b] = 0; }
     long long cum = 0;
-    for (const Tensor* t : ts) {
+    for (const UadTensor* t : ts) {
         int b = (int)((cum + t->count() / 2) * K / cnt);
         if (b >= K) b = K - 1;
         cum += t->count();
@@ -237,36 +207,6 @@ static bool k3_one_pack(const uad_gan* m) { return m->wpack3_f && m->wpack3_d &&
 const unsigned short* K3F(uad_gan* m, long long off) { return k3_one_pack(m) ? (const unsigned short*)m->wpack3_f + 4 * off : PK16F(m, off); }
 const unsigned short* K3D(uad_gan* m, long long off) { return k3_one_pack(m) ? (const unsigned short*)m->wpack3_d + 4 * off : PK16D(m, off); }
 long long PLANE(const Block& L) { return (long long)L.d.KS * L.d.KS * L.d.CB * L.d.CS; }
-UadXform no_xform() { UadXform x; x.scale = nullptr; x.shift = nullptr; x.alpha = 1.f; x.mult = 1.f; return x; }
-UadEpilogue epi_bias(const float* bias, const float* mul = nullptr, const float* add = nullptr) {
-    UadEpilogue e;
-    memset(&e, 0, sizeof e);
-    e.kind = UAD_EPI_BIAS; e.bias = bias; e.mul = mul; e.add = add;
-    return e;
-}
-UadConvDesc dense_desc(int n, int in, int out) { return UadConvDesc{n, 1, 1, in, 1, 1, out, 1, 1, 0}; }
-UadConvDesc conv1x1_desc(int n, int h, int w, int cin, int cout) { return UadConvDesc{n, h, w, cin, h, w, cout, 1, 1, 0}; }
-int ilog2i(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-inline unsigned blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
-
-long long add_tensor(uad_gan* m, const std::string& name, int rank, int s0, int s1, int s2, int s3) {
-    Tensor t;
-    t.name = name; t.off = m->nparams; t.rank = rank;
-    t.shape[0] = s0; t.shape[1] = s1; t.shape[2] = s2; t.shape[3] = s3;
-    m->nparams += t.count();
-    m->tensors.push_back(t);
-    return t.off;
-}
-int dev_alloc(uad_gan* m, float** p, size_t floats, const char* name = nullptr) {
-    void* q = nullptr;
-    if (floats == 0) floats = 4;
-    HIP_TRY(hipMalloc(&q, floats * sizeof(float)));
-    HIP_TRY(hipMemset(q, 0, floats * sizeof(float)));
-    m->allocs.push_back(q);
-    *p = (float*)q;
-    if (name) m->dbg[name] = std::make_pair((float*)q, (long long)floats);
-    return UAD_OK;
-}
 
 // ---- launch helpers ----
 template <int ACT>
@@ -1569,33 +1509,25 @@ extern "C" {
 
 int uad_gan_destroy(uad_gan_t* m) {
     if (!m) return UAD_OK;
-    const int rc = uad_ar_close(&m->ar);      // (waits for a collective still queued on the lane's stream: it reads `grads`)
-    for (void* p : m->allocs) hipFree(p);
+    const int rc = core_free(m);      // (waits for a collective still queued on the lane's stream: it reads `grads`)
     delete m;
     return rc;
 }
 long long uad_gan_param_count(const uad_gan_t* m) { return m ? m->nparams : 0; }
 int uad_gan_num_tensors(const uad_gan_t* m) { return m ? (int)m->tensors.size() : 0; }
 int uad_gan_tensor_info(const uad_gan_t* m, int idx, char* name, int name_cap, long long* offset, int* rank, int* shape4) {
-    if (!m || idx < 0 || idx >= (int)m->tensors.size()) return fail(UAD_ERR_INVALID, "tensor index out of range");
-    const Tensor& t = m->tensors[idx];
-    if (name && name_cap > 0) { strncpy(name, t.name.c_str(), name_cap - 1); name[name_cap - 1] = 0; }
-    if (offset) *offset = t.off;
-    if (rank) *rank = t.rank;
-    if (shape4) for (int i = 0; i < 4; ++i) shape4[i] = t.shape[i];
-    return UAD_OK;
+    return core_tensor_info(m, idx, name, name_cap, offset, rank, shape4);
+}
+// parameters are about to change from the host side: every pack is stale
+static void invalidate_pack(uad_gan* m) { m->packed_valid = false; m->pack_all = true; }
+static float* gan_buffer_ptr(const uad_gan* m, int which) {      // no side effect: the core's four buffers + the AnoVAE-GAN second slots
+    if (m && which == UAD_BUF_ADAM_M2) return m->adam_m2;
+    if (m && which == UAD_BUF_ADAM_V2) return m->adam_v2;
+    return core_buffer_ptr(m, which);
 }
 float* uad_gan_buffer(uad_gan_t* m, int which) {
-    if (!m) return nullptr;
-    switch (which) {
-        case UAD_BUF_PARAMS: m->packed_valid = false; m->pack_all = true; return m->params;      // the caller may write through the pointer (DP broadcast): repack before the next phase
-        case UAD_BUF_GRADS: return m->grads;
-        case UAD_BUF_ADAM_M: return m->adam_m;
-        case UAD_BUF_ADAM_V: return m->adam_v;
-        case UAD_BUF_ADAM_M2: return m->adam_m2;
-        case UAD_BUF_ADAM_V2: return m->adam_v2;
-    }
-    return nullptr;
+    if (m && which == UAD_BUF_PARAMS) invalidate_pack(m);      // the caller may write through the pointer (DP broadcast): repack before the next phase
+    return gan_buffer_ptr(m, which);
 }
 int uad_gan_group(const uad_gan_t* m, int group, long long* offset, long long* count) {
     if (m && group == UAD_GAN_GROUP_VAE) {       // Encoder | Generator are adjacent in the flat buffers
@@ -1609,22 +1541,14 @@ int uad_gan_group(const uad_gan_t* m, int group, long long* offset, long long* c
     return UAD_OK;
 }
 int uad_gan_set_buffer(uad_gan_t* m, int which, const float* host, long long count) {
-    float* p = uad_gan_buffer(m, which);
-    if (!p || !host || count != m->nparams) return fail(UAD_ERR_INVALID, "gan set_buffer: bad arguments (count=%lld, expected %lld)", count, m ? m->nparams : -1);
-    HIP_TRY(hipMemcpy(p, host, (size_t)count * sizeof(float), hipMemcpyHostToDevice));
-    if (which == UAD_BUF_PARAMS) { m->packed_valid = false; m->pack_all = true; }
-    return UAD_OK;
+    return core_set_buffer(m, "gan set_buffer", gan_buffer_ptr(m, which), host, count, [&] { if (which == UAD_BUF_PARAMS) invalidate_pack(m); });
 }
-int uad_gan_get_buffer(uad_gan_t* m, int which, float* host, long long count) {
-    float* p = uad_gan_buffer(m, which);
-    if (!p || !host || count != m->nparams) return fail(UAD_ERR_INVALID, "gan get_buffer: bad arguments");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(host, p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
-    return UAD_OK;
+int uad_gan_get_buffer(uad_gan_t* m, int which, float* host, long long count) {      // a read: the packs stay valid (checkpoint save)
+    return core_get_buffer(m, "gan get_buffer", gan_buffer_ptr(m, which), host, count, [] { return UAD_OK; });
 }
 int uad_gan_set_math_mode(uad_gan_t* m, int mode) {
     if (!m || (mode != UAD_MATH_F32 && mode != UAD_MATH_BF16X3 && mode != UAD_MATH_BF16X3_ALL)) return fail(UAD_ERR_INVALID, "bad math mode");
-    m->math = mode == UAD_MATH_F32 ? UAD_MATH_F32 : UAD_MATH_BF16X3; m->generic16 = mode == UAD_MATH_BF16X3_ALL; m->packed_valid = false; m->pack_all = true;
+    m->math = mode == UAD_MATH_F32 ? UAD_MATH_F32 : UAD_MATH_BF16X3; m->generic16 = mode == UAD_MATH_BF16X3_ALL; invalidate_pack(m);
     return UAD_OK;
 }
 long long uad_gan_get_step(const uad_gan_t* m, int group) { return (m && group >= 0 && group < 3) ? m->step[group] : 0; }
@@ -1887,9 +1811,6 @@ int uad_gan_reconstruct(uad_gan_t* m, const uad_gan_io_t* io, int n, void* strea
     if (!m || !io) return fail(UAD_ERR_INVALID, "null argument");
     return gan_reconstruct_body(m, io, n, stream);
 }
-int uad_k3_profile_enable(int on) { uad_k3_prof_enable(on != 0); return UAD_OK; }
-int uad_k3_profile_read(char* buf, int cap) { return uad_k3_prof_read(buf, cap); }
-
 int uad_gan_adam(uad_gan_t* m, int group, float lr, float beta1, float beta2, float eps, float grad_scale, void* stream) {
     if (!m || group < 0 || group > 2) return fail(UAD_ERR_INVALID, "bad group");
     m->step[group] += 1;

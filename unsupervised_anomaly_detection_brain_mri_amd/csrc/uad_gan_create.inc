@@ -1,16 +1,33 @@
 // uad_gan_create.inc -- uad_gan_create and the per-variant constructors (parameter tables in TF first-call order, device buffers, workspace
 // sizing) of the materialised-graph handle; included by uad_gan.hip inside its extern "C" block.  Not a translation unit of its own.
+// Each constructor is gan_new, its parameter table, gan_alloc_flat, then its own activations and scratch.
+// What every constructor starts from.  packs: the graph has k5 layers, whose packed copies refresh_packs keeps (stale until the first phase); without
+// them nothing is ever packed.
+static uad_gan* gan_new(const uad_gan_config_t* cfg, int variant, int npool, bool packs) {
+    uad_gan* m = new uad_gan();
+    m->cfg = *cfg; m->variant = variant; m->npool = npool; m->exact_from = -1;
+    m->nparams = 0; m->math = UAD_MATH_F32; m->packed_valid = !packs; m->pack_all = packs; m->dirty_lo = (1ll << 62); m->dirty_hi = -1;
+    m->step[0] = m->step[1] = m->step[2] = 0;
+    return m;
+}
+// ... and, once its parameter table stands, the flat buffers of the core (the packs: a handle gan_new was told has them)
+static int gan_alloc_flat(uad_gan* m) {
+    const size_t n = (size_t)m->nparams;
+    int rc = dev_alloc(m, &m->params, n, "params");
+    if (rc == UAD_OK) rc = dev_alloc(m, &m->grads, n, "grads");
+    for (float** p : {&m->adam_m, &m->adam_v}) if (rc == UAD_OK) rc = dev_alloc(m, p, n);
+    if (m->pack_all) for (float** p : {&m->wpack_f, &m->wpack_d, &m->wpack16_f, &m->wpack16_d}) if (rc == UAD_OK) rc = dev_alloc(m, p, n);
+    return rc;
+}
+
 // ---- handle of the ResNet variant (models/fanogan_schlegl.py); parameter table in TF first-call order ----
 static int create_resnet(const uad_gan_config_t* cfg, uad_gan_t** out) {
     const int H = cfg->height, ir = cfg->inter_res, dim = cfg->dim > 0 ? cfg->dim : 64;
     if (H != 8 * ir) return fail(UAD_ERR_UNSUPPORTED, "ResNet f-AnoGAN: the generator upsamples 8x, height must be 8 * inter_res (fanogan_schlegl.py:28,121-133)");
     if (dim % 32 || dim > 64) return fail(UAD_ERR_UNSUPPORTED, "ResNet f-AnoGAN: dim must be 32 or 64");
     if (ir < 2) return fail(UAD_ERR_UNSUPPORTED, "inter_res >= 2 needed");
-    uad_gan* m = new uad_gan();
-    m->exact_from = -1;
-    m->cfg = *cfg; m->variant = 1; m->dim = dim; m->generic16 = false; m->adam_m2 = m->adam_v2 = nullptr; m->e_sw = m->e_sb = -1;
-    m->npool = 3; m->nparams = 0; m->math = UAD_MATH_F32; m->packed_valid = false; m->pack_all = true; m->dirty_lo = (1ll << 62); m->dirty_hi = -1;
-    m->step[0] = m->step[1] = m->step[2] = 0;
+    uad_gan* m = gan_new(cfg, 1, 3, true);
+    m->dim = dim; m->generic16 = false; m->adam_m2 = m->adam_v2 = nullptr; m->e_sw = m->e_sb = -1;
     char nm[160];
     int cin = 1, res = H;
     for (int i = 0; i < 3; ++i) {
@@ -100,12 +117,8 @@ static int create_resnet(const uad_gan_config_t* cfg, uad_gan_t** out) {
 
     // ---- device memory ----
     const size_t NB = (size_t)cfg->max_batch, HW = (size_t)H * H;
-    int rc = UAD_OK;
+    int rc = gan_alloc_flat(m);
 #define ALLOC(ptr, n, name) if (rc == UAD_OK) rc = dev_alloc(m, &(ptr), (n), name)
-    ALLOC(m->params, (size_t)m->nparams, "params"); ALLOC(m->grads, (size_t)m->nparams, "grads");
-    ALLOC(m->adam_m, (size_t)m->nparams, nullptr); ALLOC(m->adam_v, (size_t)m->nparams, nullptr);
-    ALLOC(m->wpack_f, (size_t)m->nparams, nullptr); ALLOC(m->wpack_d, (size_t)m->nparams, nullptr);
-    ALLOC(m->wpack16_f, (size_t)m->nparams, nullptr); ALLOC(m->wpack16_d, (size_t)m->nparams, nullptr);
     if (!getenv("UAD_NO_X6")) {       // three-plane packs of the k3 kernels for the bf16x6 exact passes (UAD_NO_X6=1: those passes on the fp32 MFMA kernels)
         ALLOC(m->wpack3_f, (size_t)m->nparams * 2, nullptr); ALLOC(m->wpack3_d, (size_t)m->nparams * 2, nullptr);
     }
@@ -193,14 +206,11 @@ static int create_zimmerer(const uad_gan_config_t* cfg, uad_gan_t** out) {
     const int H = cfg->height, zd = cfg->zdim;
     if (H < 32 || H % 16) return fail(UAD_ERR_UNSUPPORTED, "Zimmerer VAE: height must be a power of two >= 32");
     if (cfg->inter_res != H / 16) return fail(UAD_ERR_INVALID, "Zimmerer VAE: intermediateResolutions must be height / 16 (four stride-2 stages)");
-    uad_gan* m = new uad_gan();
-    m->exact_from = -1;
+    uad_gan* m = gan_new(cfg, UAD_GAN_AAE, 4, false);
     const bool ce = cfg->aae_kind == 5;
     const std::string se = ce ? "Encoder/" : "", sb = ce ? "Bottleneck/" : "", sdc = ce ? "Decoder/" : "";
-    m->cfg = *cfg; m->variant = UAD_GAN_AAE; m->aae_kind = cfg->aae_kind; m->zim = true; m->zim_ce = ce; m->gmv = false; m->a_constrained = m->a_critic = false;
+    m->aae_kind = cfg->aae_kind; m->zim = true; m->zim_ce = ce; m->gmv = false; m->a_constrained = m->a_critic = false;
     m->dim = 0; m->generic16 = false; m->adam_m2 = m->adam_v2 = nullptr; m->e_sw = m->e_sb = -1; m->a_zw = m->a_zb = -1;
-    m->npool = 4; m->nparams = 0; m->math = UAD_MATH_F32; m->packed_valid = true; m->pack_all = false; m->dirty_lo = (1ll << 62); m->dirty_hi = -1;        // nothing is packed: no k5 layers
-    m->step[0] = m->step[1] = m->step[2] = 0;
     static const int ef[4] = {16, 64, 256, 1024}, gf[4] = {1024, 256, 64, 16};
     char nm[160];
     int cin = 1, res = H;
@@ -235,10 +245,8 @@ static int create_zimmerer(const uad_gan_config_t* cfg, uad_gan_t** out) {
     for (int k = 0; k < 3; ++k) { m->grp_off[k] = 0; m->grp_cnt[k] = m->nparams; }      // one optimizer over every variable
 
     const size_t NB = (size_t)cfg->max_batch * (ce ? 2 : 1), HW = (size_t)H * H;      // ceVAE: both branches in one pass
-    int rc = UAD_OK;
+    int rc = gan_alloc_flat(m);
 #define ALLOC(ptr, n, name) if (rc == UAD_OK) rc = dev_alloc(m, &(ptr), (n), name)
-    ALLOC(m->params, (size_t)m->nparams, "params"); ALLOC(m->grads, (size_t)m->nparams, "grads");
-    ALLOC(m->adam_m, (size_t)m->nparams, nullptr); ALLOC(m->adam_v, (size_t)m->nparams, nullptr);
     m->wpack_f = m->wpack_d = m->wpack16_f = m->wpack16_d = nullptr;
     m->a_xcat = m->z_l1 = nullptr;
     if (ce) { ALLOC(m->a_xcat, NB * HW, nullptr); ALLOC(m->z_l1, NB * HW, nullptr); }
@@ -295,13 +303,10 @@ static int create_you(const uad_gan_config_t* cfg, uad_gan_t** out) {
     // the first decoder convolution contracts over dim_z channels: 1 (image-side kernel) or a multiple of 8 (generic kernels' K step)
     if (!(Z == 1 || Z % 8 == 0) || Z > 64 || W < 1 || W > 64 || C < 1 || C > 64 || (long long)Z * C > 1024)
         return fail(UAD_ERR_UNSUPPORTED, "GMVAE (You): dim_z 1 or a multiple of 8 (<= 64), dim_w <= 64, dim_c <= 64, dim_z * dim_c <= 1024");
-    uad_gan* m = new uad_gan();
-    m->exact_from = -1;
-    m->cfg = *cfg; m->variant = UAD_GAN_AAE; m->aae_kind = 6; m->you = true; m->zim = m->zim_ce = m->gmv = false; m->a_constrained = m->a_critic = false;
+    uad_gan* m = gan_new(cfg, UAD_GAN_AAE, 2, false);
+    m->aae_kind = 6; m->you = true; m->zim = m->zim_ce = m->gmv = false; m->a_constrained = m->a_critic = false;
     m->gm_W = W; m->gm_Z = Z; m->gm_C = C;
     m->dim = C; m->generic16 = false; m->adam_m2 = m->adam_v2 = nullptr; m->e_sw = m->e_sb = -1; m->a_zw = m->a_zb = -1;
-    m->npool = 2; m->nparams = 0; m->math = UAD_MATH_F32; m->packed_valid = true; m->pack_all = false; m->dirty_lo = (1ll << 62); m->dirty_hi = -1;
-    m->step[0] = m->step[1] = m->step[2] = 0;
     auto conv_op = [&](const std::string& name, int kind, int hin, int cin, int cout, int stride, bool relu) {
         YOp o;
         o.kind = kind; o.relu = relu; o.c = o.a = nullptr;
@@ -356,11 +361,9 @@ static int create_you(const uad_gan_config_t* cfg, uad_gan_t** out) {
     m->flat = r * r * Z; m->cenc = 64; m->cmid = 64;
 
     const size_t NB = (size_t)cfg->max_batch, HW = (size_t)H * H, Lm = NB * r * r;
-    int rc = UAD_OK;
+    int rc = gan_alloc_flat(m);
     char nm[64];
 #define ALLOC(ptr, n, name) if (rc == UAD_OK) rc = dev_alloc(m, &(ptr), (n), name)
-    ALLOC(m->params, (size_t)m->nparams, "params"); ALLOC(m->grads, (size_t)m->nparams, "grads");
-    ALLOC(m->adam_m, (size_t)m->nparams, nullptr); ALLOC(m->adam_v, (size_t)m->nparams, nullptr);
     m->wpack_f = m->wpack_d = m->wpack16_f = m->wpack16_d = nullptr;
     size_t maxact = NB * HW * 64;
     for (size_t i = 0; i < m->y_enc.size(); ++i) {
@@ -417,12 +420,9 @@ static int create_chen(const uad_gan_config_t* cfg, uad_gan_t** out) {
     if (dim % 32 || dim > 64) return fail(UAD_ERR_UNSUPPORTED, "constrained AAE (Chen): dim must be 32 or 64");
     if (ir < 2) return fail(UAD_ERR_UNSUPPORTED, "inter_res >= 2 needed");
     if (zd > kCritMaxZ) return fail(UAD_ERR_UNSUPPORTED, "zDim <= %d", kCritMaxZ);
-    uad_gan* m = new uad_gan();
-    m->exact_from = -1;
-    m->cfg = *cfg; m->variant = UAD_GAN_AAE; m->aae_kind = 7; m->chen = true; m->dim = dim; m->generic16 = false; m->e_sw = m->e_sb = -1;
+    uad_gan* m = gan_new(cfg, UAD_GAN_AAE, 3, false);
+    m->aae_kind = 7; m->chen = true; m->dim = dim; m->generic16 = false; m->e_sw = m->e_sb = -1;
     m->a_constrained = true; m->a_critic = true; m->a_h1 = 400; m->a_h2 = 200;
-    m->npool = 3; m->nparams = 0; m->math = UAD_MATH_F32; m->packed_valid = true; m->pack_all = false; m->dirty_lo = (1ll << 62); m->dirty_hi = -1;
-    m->step[0] = m->step[1] = m->step[2] = 0;
     char nm[160];
     int ln = 0;
     std::map<std::string, int> cnt;
@@ -499,10 +499,8 @@ static int create_chen(const uad_gan_config_t* cfg, uad_gan_t** out) {
     m->grp_off[2] = ae_end; m->grp_cnt[2] = m->nparams - ae_end;
 
     const size_t NB = (size_t)cfg->max_batch, E2 = 2 * NB, HW = (size_t)H * H;
-    int rc = UAD_OK;
+    int rc = gan_alloc_flat(m);
 #define ALLOC(ptr, n, name) if (rc == UAD_OK) rc = dev_alloc(m, &(ptr), (n), name)
-    ALLOC(m->params, (size_t)m->nparams, "params"); ALLOC(m->grads, (size_t)m->nparams, "grads");
-    ALLOC(m->adam_m, (size_t)m->nparams, nullptr); ALLOC(m->adam_v, (size_t)m->nparams, nullptr);
     ALLOC(m->adam_m2, (size_t)m->nparams, nullptr); ALLOC(m->adam_v2, (size_t)m->nparams, nullptr);
     m->wpack_f = m->wpack_d = m->wpack16_f = m->wpack16_d = nullptr;
     size_t maxact = NB * HW * dim, max_ta = 0, max_tb = 0, max_sp = 0;
@@ -580,14 +578,11 @@ static int create_aae(const uad_gan_config_t* cfg, uad_gan_t** out) {
     const int npool = ilog2i(H) - ilog2i(ir);
     if (npool < 2 || npool > 5) return fail(UAD_ERR_UNSUPPORTED, "log2(height/inter_res) = %d: 2..5 blocks supported", npool);
     if (!gmv && cfg->zdim > kCritMaxZ) return fail(UAD_ERR_UNSUPPORTED, "zDim <= %d", kCritMaxZ);
-    uad_gan* m = new uad_gan();
-    m->exact_from = -1;
+    uad_gan* m = gan_new(cfg, UAD_GAN_AAE, npool, true);
     m->gmv = gmv; m->gm_W = cfg->dim_w; m->gm_Z = cfg->zdim; m->gm_C = cfg->dim; m->gm_J = 2 * cfg->dim_w + 2 * cfg->zdim;
-    m->cfg = *cfg; m->variant = UAD_GAN_AAE; m->dim = 0; m->generic16 = false; m->adam_m2 = m->adam_v2 = nullptr; m->e_sw = m->e_sb = -1;
+    m->dim = 0; m->generic16 = false; m->adam_m2 = m->adam_v2 = nullptr; m->e_sw = m->e_sb = -1;
     m->aae_kind = cfg->aae_kind; m->a_constrained = cfg->aae_kind == 0 || cfg->aae_kind == 2; m->a_critic = cfg->aae_kind == 1 || cfg->aae_kind == 2;
     m->a_h1 = cfg->aae_kind == 2 ? 100 : 50; m->a_h2 = 50;
-    m->npool = npool; m->nparams = 0; m->math = UAD_MATH_F32; m->packed_valid = false; m->pack_all = true; m->dirty_lo = (1ll << 62); m->dirty_hi = -1;
-    m->step[0] = m->step[1] = m->step[2] = 0;
     char nm[160];
     int cin = 1, res = H;
     for (int i = 0; i < npool; ++i) {
@@ -667,13 +662,9 @@ static int create_aae(const uad_gan_config_t* cfg, uad_gan_t** out) {
     m->grp_off[2] = ae_end; m->grp_cnt[2] = m->nparams - ae_end;
 
     const size_t NB = (size_t)cfg->max_batch, HW = (size_t)H * H, E2 = m->a_constrained ? 2 * NB : NB;
-    int rc = UAD_OK;
+    int rc = gan_alloc_flat(m);
 #define ALLOC(ptr, n, name) if (rc == UAD_OK) rc = dev_alloc(m, &(ptr), (n), name)
-    ALLOC(m->params, (size_t)m->nparams, "params"); ALLOC(m->grads, (size_t)m->nparams, "grads");
-    ALLOC(m->adam_m, (size_t)m->nparams, nullptr); ALLOC(m->adam_v, (size_t)m->nparams, nullptr);
     ALLOC(m->adam_m2, (size_t)m->nparams, nullptr); ALLOC(m->adam_v2, (size_t)m->nparams, nullptr);
-    ALLOC(m->wpack_f, (size_t)m->nparams, nullptr); ALLOC(m->wpack_d, (size_t)m->nparams, nullptr);
-    ALLOC(m->wpack16_f, (size_t)m->nparams, nullptr); ALLOC(m->wpack16_d, (size_t)m->nparams, nullptr);
     size_t maxact = NB * HW;
     m->ec.resize(npool); m->ea.resize(npool + 1, nullptr); m->a_eg.resize(npool); m->a_cp.resize(npool);
     for (int i = 0; i < npool; ++i) {
@@ -749,12 +740,9 @@ int uad_gan_create(const uad_gan_config_t* cfg, uad_gan_t** out) {
     if (npool < 2 || npool > 5) return fail(UAD_ERR_UNSUPPORTED, "log2(height/inter_res) = %d: 2..5 blocks supported", npool);
     if (H < 32) return fail(UAD_ERR_UNSUPPORTED, "height >= 32 needed");
 
-    uad_gan* m = new uad_gan();
-    m->exact_from = -1;
-    m->cfg = *cfg; m->variant = cfg->variant; m->dim = 0; m->generic16 = false;
+    uad_gan* m = gan_new(cfg, cfg->variant, npool, true);
+    m->dim = 0; m->generic16 = false;
     const bool av = cfg->variant == UAD_GAN_ANOVAEGAN;
-    m->npool = npool; m->nparams = 0; m->math = UAD_MATH_F32; m->packed_valid = false; m->pack_all = true; m->dirty_lo = (1ll << 62); m->dirty_hi = -1;
-    m->step[0] = m->step[1] = m->step[2] = 0;
     const int ir = cfg->inter_res;
     char nm[160];
     // ---- parameter table, TF variable-creation order (fanogan.py:15-58) ----
@@ -832,12 +820,8 @@ int uad_gan_create(const uad_gan_config_t* cfg, uad_gan_t** out) {
 
     // ---- device memory ----
     const size_t NB = (size_t)cfg->max_batch, HW = (size_t)H * H;
-    int rc = UAD_OK;
+    int rc = gan_alloc_flat(m);
 #define ALLOC(ptr, n, name) if (rc == UAD_OK) rc = dev_alloc(m, &(ptr), (n), name)
-    ALLOC(m->params, (size_t)m->nparams, "params"); ALLOC(m->grads, (size_t)m->nparams, "grads");
-    ALLOC(m->adam_m, (size_t)m->nparams, nullptr); ALLOC(m->adam_v, (size_t)m->nparams, nullptr);
-    ALLOC(m->wpack_f, (size_t)m->nparams, nullptr); ALLOC(m->wpack_d, (size_t)m->nparams, nullptr);
-    ALLOC(m->wpack16_f, (size_t)m->nparams, nullptr); ALLOC(m->wpack16_d, (size_t)m->nparams, nullptr);
     size_t maxact = 3 * NB * HW;
     m->ec.resize(npool); m->ea.resize(npool + 1, nullptr);
     for (int i = 0; i < npool; ++i) {

@@ -193,12 +193,6 @@ inline int hc_lab_vec(const float* in, const uint8_t* labels) {
 #if defined(__HIP__) && !defined(UAD_HOST_EMULATION)
 #define fail uad_fail
 
-#define HC_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 extern "C" {
 
 size_t uad_histogram_by_class_workspace(long long n) {
@@ -218,11 +212,11 @@ int uad_histogram_by_class(const float* in, const uint8_t* labels, long long n, 
     if (n > HC_MAX_N) return fail(UAD_ERR_UNSUPPORTED, "histogram_by_class: at most 2^31 - 1 values, got %lld", n);
     if (((uintptr_t)in & 3) != 0) return fail(UAD_ERR_INVALID, "histogram_by_class: input must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (bins > 0) HC_TRY(hipMemsetAsync(counts, 0, (size_t)n_classes * bins * sizeof(long long), st));
+    if (bins > 0) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_classes * bins * sizeof(long long), st));
     if (n == 0) {
         if (sums) {
-            HC_TRY(hipMemsetAsync(class_count, 0, (size_t)n_classes * sizeof(long long), st));
-            HC_TRY(hipMemsetAsync(sums, 0, (size_t)n_classes * sizeof(double), st));
+            HIP_TRY(hipMemsetAsync(class_count, 0, (size_t)n_classes * sizeof(long long), st));
+            HIP_TRY(hipMemsetAsync(sums, 0, (size_t)n_classes * sizeof(double), st));
         }
         return UAD_OK;
     }
@@ -235,10 +229,10 @@ int uad_histogram_by_class(const float* in, const uint8_t* labels, long long n, 
     HcPartial* partials = sums ? (HcPartial*)workspace : nullptr;      // every tile's partial is written by the first kernel: no initialisation
     hipLaunchKernelGGL(hist_class_kernel, dim3(hc_grid(tiles)), dim3(HC_THREADS), 0, st, in, labels, (unsigned long long)n, n_classes, edges, bins, centre,
                        (unsigned long long*)counts, partials, tiles, hc_lab_vec(in, labels));
-    HC_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (sums) {
         hipLaunchKernelGGL(hist_class_finish_kernel, dim3(1), dim3(HC_THREADS), 0, st, partials, tiles, n_classes, class_count, sums);
-        HC_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return UAD_OK;
 }

@@ -6,8 +6,14 @@
 #ifndef UAD_HOST_EMULATION      // a host emulation of tests/native/ takes only the generator at the end of this file
 #include <hip/hip_runtime.h>
 
-// records the message uad_last_error() returns and hands `code` back (uad_model.hip); the entry points' `return fail(...)`
+// records the message uad_last_error() returns and hands `code` back (uad_ops.hip); the entry points' `return fail(...)`
 int uad_fail(int code, const char* fmt, ...);
+// the launch layers' check of a HIP call: a failure leaves the entry point with UAD_ERR_HIP (include/uad_hip.h) and the call's text in the message
+#define HIP_TRY(expr)                                                                                      \
+    do {                                                                                                   \
+        hipError_t e_ = (expr);                                                                            \
+        if (e_ != hipSuccess) return uad_fail(UAD_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
 
 // One strided-conv relation between a "big" (finer grid) and a "small" image:
 //   big pixel  (S*i - P + ky, S*j - P + kx)  <->  small pixel (i, j),  tap (ky,kx)

@@ -1,0 +1,375 @@
+// The part of the C-ABI (include/uad_hip.h) that takes no model handle: the library's error message and version, the stand-alone device ops
+// (residual, counter-based random fill, clock probe, slice / mask gathers), the op-level entry points uad_op_* that run ONE launch of the
+// kernels of uad_gemm.hip / uad_misc.hip on caller-supplied tensors (weight packs and workspace built on the fly, synchronous: tests and
+// tools), and the k3 kernel's in-kernel profile switch.  Host-only: no kernel is defined here.
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+
+#include "uad_handle.h"      // fail, no_xform, epi_bias (the launch-argument helpers the handles use too); no handle is touched here
+
+static thread_local std::string g_err;
+
+// records the message uad_last_error() returns; declared in uad_kernels.h for every launch layer
+int uad_fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+
+extern "C" {
+
+const char* uad_last_error(void) { return g_err.c_str(); }
+const char* uad_version(void) { return "uad_hip 0.1 (gfx950, fp32 MFMA)"; }
+
+int uad_k3_profile_enable(int on) { uad_k3_prof_enable(on != 0); return UAD_OK; }
+int uad_k3_profile_read(char* buf, int cap) { return uad_k3_prof_read(buf, cap); }
+
+int uad_residual(const float* x, const float* xr, const float* mask, int n, int hw, int pos_only, float prior_thresh,
+                 float* out, float* l1err, void* stream) {
+    if (!x || !xr || !out || n <= 0 || hw <= 0) return fail(UAD_ERR_INVALID, "uad_residual: bad arguments");
+    uad_launch_residual(x, xr, mask, n, hw, pos_only, prior_thresh, out, l1err, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_rng_fill(const uad_rng_job_t* jobs, int njobs, int n, unsigned long long seed, unsigned long long step, long long sample0, void* stream) {
+    if (!jobs || njobs <= 0 || njobs > 8 || n <= 0 || sample0 < 0) return fail(UAD_ERR_INVALID, "rng_fill: 1..8 jobs, n > 0, sample0 >= 0");
+    UadRngJob js[8];
+    for (int i = 0; i < njobs; ++i) {
+        if (!jobs[i].out || jobs[i].per_sample <= 0 || (jobs[i].kind != UAD_RNG_NORMAL && jobs[i].kind != UAD_RNG_KEEP_MASK))
+            return fail(UAD_ERR_INVALID, "rng_fill: job %d: null output, empty sample or unknown kind", i);
+        if (jobs[i].kind == UAD_RNG_KEEP_MASK && !(jobs[i].rate >= 0.f && jobs[i].rate < 1.f)) return fail(UAD_ERR_INVALID, "rng_fill: dropout rate must be in [0, 1)");
+        js[i] = UadRngJob{jobs[i].out, jobs[i].per_sample, jobs[i].kind, jobs[i].rate, jobs[i].stream};
+    }
+    uad_launch_rng_fill(js, njobs, n, seed, step, sample0, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_clock_probe(unsigned long long* out2, unsigned long long ticks_100mhz, void* stream) {
+    if (!out2 || ticks_100mhz == 0 || ticks_100mhz > 1000000000ull) return fail(UAD_ERR_INVALID, "clock_probe: null output or a duration outside (0, 10 s]");
+    uad_launch_clock_probe(out2, ticks_100mhz, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_gather_slices(const float* src, const int* idx, int n, long long slice_elems, float* out, void* stream) {
+    if (!src || !idx || !out || n <= 0 || slice_elems <= 0 || slice_elems % 4) return fail(UAD_ERR_INVALID, "gather_slices: bad arguments (slice elements must be a multiple of 4)");
+    if (n > 65535) return fail(UAD_ERR_UNSUPPORTED, "gather_slices: at most 65535 slices per call");
+    uad_launch_gather_slices(src, idx, n, slice_elems, out, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+int uad_gather_mask(const unsigned char* labels, const int* idx, int n, long long slice_px, const unsigned char* lut256, float* out, void* stream) {
+    if (!labels || !idx || !out || n <= 0 || slice_px <= 0) return fail(UAD_ERR_INVALID, "gather_mask: bad arguments");
+    if (n > 65535) return fail(UAD_ERR_UNSUPPORTED, "gather_mask: at most 65535 slices per call");
+    uad_launch_gather_mask(labels, idx, n, slice_px, lut256, out, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ op-level entry points
+static UadConvDesc to_desc(const uad_conv_desc_t* d) { return UadConvDesc{d->N, d->HB, d->WB, d->CB, d->HS, d->WS, d->CS, d->KS, d->S, d->P}; }
+static UadXform to_xf(const uad_xform_t* x) {
+    UadXform r; r.scale = x ? x->scale : nullptr; r.shift = x ? x->shift : nullptr; r.alpha = x ? x->alpha : 1.f; r.mult = 1.f;
+    return r;
+}
+static int check_gemm_desc(const uad_conv_desc_t* d, bool f_type) {
+    if (!d) return fail(UAD_ERR_INVALID, "null desc");
+    const int ca = f_type ? d->CB : d->CS, nn = f_type ? d->CS : d->CB;
+    if (ca % 8 || nn % 4) return fail(UAD_ERR_UNSUPPORTED, "contraction channels must be a multiple of 8 and output channels of 4");
+    return UAD_OK;
+}
+
+// op-level helpers: the spatial kernels need the packed weight copy; build it on the fly (synchronous, tests only)
+// UAD_MATH of the op-level entry points: unset / "f32" = exact fp32, "bf16x3", or "bf16x6" = three-plane products on the k3 tap-list kernel and on the k5 s2
+// spatial kernels where they take the launch (the exact-fp32 route for a k5 launch they refuse, everything else as bf16x3)
+static bool op_bf16x6() { const char* e = getenv("UAD_MATH"); return e && !strcmp(e, "bf16x6"); }
+static bool op_bf16x3() { const char* e = getenv("UAD_MATH"); return e && (!strcmp(e, "bf16x3") || !strcmp(e, "bf16x6")); }
+static int op_math() { return op_bf16x6() ? UAD_MATH_BF16X6 : op_bf16x3() ? UAD_MATH_BF16X3 : UAD_MATH_F32; }
+static bool op_k5(const UadConvDesc& d, bool f_type) { return d.KS == 5 && uad_conv_spatial_ok(d, f_type); }
+// plain: identity activation on load, bias (+ addend) epilogue without `mul` -- what the k3 tap-list kernel takes besides the shape (uad_convk16.inc:
+// convk16_takes); any other launch of a k3 shape runs the generic kernels, which understand TWO planes only.  A k5 s2 launch of the spatial kernels is handed
+// three planes AND the fp32 pack: the launcher's own decision (plan_for / x6_route / d_x6_form_ok) picks the route, and no route is left without its operand.
+static int op_planes(const UadConvDesc& d, bool f_type, bool plain) {
+    if (!op_bf16x6()) return 2;
+    return ((plain && uad_conv_k3_takes(d, f_type)) || op_k5(d, f_type)) ? 3 : 2;
+}
+// the workspace a launch is given: slabs + (behind them) the arrival counters of the in-kernel reduction -- the same path as the model handle.  Shape only (plan
+// query), or allocated and zeroed (launch).
+static const int kOpCounters = 16384;
+static UadGemmWs op_ws_shape(const UadConvDesc& d, bool f_type, bool have_pack) {
+    static float some;      // a plan query only tests the pointers for presence
+    UadGemmWs ws;
+    ws.ptr = nullptr; ws.floats = uad_conv_ws_floats(d, f_type, have_pack); ws.counters = nullptr; ws.ncounters = 0;
+    if (ws.floats) { ws.ptr = &some; ws.counters = reinterpret_cast<unsigned*>(&some); ws.ncounters = kOpCounters; }
+    return ws;
+}
+static int ws_for_op(const UadConvDesc& d, bool f_type, bool have_pack, UadGemmWs* ws) {
+    *ws = op_ws_shape(d, f_type, have_pack);
+    ws->ptr = nullptr; ws->counters = nullptr;
+    if (ws->floats) {
+        HIP_TRY(hipMalloc((void**)&ws->ptr, (ws->floats + kOpCounters) * sizeof(float)));
+        HIP_TRY(hipMemset(ws->ptr + ws->floats, 0, kOpCounters * sizeof(float)));
+        ws->counters = reinterpret_cast<unsigned*>(ws->ptr + ws->floats);
+    }
+    return UAD_OK;
+}
+// the packs of one tensor in the selected math mode: p32 (fp32 pack) and / or p16 (two or three bf16 planes), F and D layout each
+struct OpPacks {
+    float *f32 = nullptr, *d32 = nullptr, *f16 = nullptr, *d16 = nullptr;
+    int planes = 2;
+    void release() { (void)hipFree(f32); (void)hipFree(d32); (void)hipFree(f16); (void)hipFree(d16); f32 = d32 = f16 = d16 = nullptr; }
+    bool any() const { return f32 || f16; }
+};
+static bool op_has32(const UadConvDesc& d, bool f_type, int planes) { return uad_conv_spatial_ok(d, f_type) && (!op_bf16x3() || (planes == 3 && op_k5(d, f_type))); }
+static bool op_has16(const UadConvDesc& d, bool f_type) { return uad_conv_spatial_ok(d, f_type) && op_bf16x3(); }
+static int pack_for_op(const UadConvDesc& d, const float* W, bool f_type, OpPacks* pk, hipStream_t st, bool plain = false) {
+    *pk = OpPacks();
+    pk->planes = op_planes(d, f_type, plain);
+    const size_t n = (size_t)d.KS * d.KS * d.CB * d.CS;
+    long long off = 0; int cb = d.CB, cs = d.CS, taps = d.KS * d.KS;
+    if (op_has32(d, f_type, pk->planes)) {
+        HIP_TRY(hipMalloc((void**)&pk->f32, n * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&pk->d32, n * sizeof(float)));
+        uad_launch_pack_weights(W, pk->f32, pk->d32, &off, &cb, &cs, &taps, 1, st);
+    }
+    if (op_has16(d, f_type)) {
+        HIP_TRY(hipMalloc((void**)&pk->f16, 2 * n * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&pk->d16, 2 * n * sizeof(float)));
+        if (pk->planes == 3) uad_launch_pack_weights_bf16_3p(W, (unsigned short*)pk->f16, (unsigned short*)pk->d16, &off, &cb, &cs, &taps, 1, st);
+        else uad_launch_pack_weights_bf16(W, (unsigned short*)pk->f16, (unsigned short*)pk->d16, &off, &cb, &cs, &taps, 1, st);
+    }
+    return UAD_OK;
+}
+// launch arguments for the op-level entry points in the selected math mode
+#define OP_PACK_ARGS(pk, d, f) ((f) ? (pk).f32 : (pk).d32), ws, (const unsigned short*)((f) ? (pk).f16 : (pk).d16), \
+                               (long long)(d).KS * (d).KS * (d).CB * (d).CS, op_bf16x3(), (pk).planes
+static int finish_op(OpPacks& pk, hipStream_t st, float* wsp = nullptr) {
+    if (pk.any() || wsp) { HIP_TRY(hipStreamSynchronize(st)); pk.release(); (void)hipFree(wsp); }
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+// What an F / D entry point would launch, from the launchers' own decision functions; out[12] as include/uad_hip.h describes uad_op_conv_plan.
+// plain: see op_planes.  fb: F kind, final backward on load.
+static void op_plan_fd(const UadConvDesc& d, bool f_type, const UadEpilogue& ep, bool has_xf, bool plain, bool fb, long long* out) {
+    const int planes = op_planes(d, f_type, plain);
+    const bool has32 = op_has32(d, f_type, planes), has16 = op_has16(d, f_type);
+    const UadGemmWs ws = op_ws_shape(d, f_type, has32 || has16);
+    for (int i = 0; i < 12; ++i) out[i] = 0;
+    uad_conv_plan_query(d, f_type, has32 || has16, ws.ptr ? ws.floats : 0, (has16 && ws.counters) ? ws.ncounters : 0, planes,
+                        f_type || uad_conv_d_x6_form_ok(ep, has_xf), out);
+    out[6] = 0; out[7] = 0; out[9] = 0; out[10] = op_math(); out[11] = 0;
+    const bool on16 = has16 && out[5] != 0;      // the launch runs on bf16 planes (a refused three-plane route runs on the fp32 pack)
+    if (f_type) {
+        // final backward on load: the F-kind spatial kernels on bf16 planes, one bit per channel of a 32-bit word, and no three-plane 64-column instance
+        if (fb && !(on16 && out[0] == 1 && d.CB <= 32 && has_xf && !(out[5] == 1 && out[3] == 64))) out[9] = 1;
+        return;
+    }
+    long long k[4];
+    uad_conv_d_kernel_query(d, has_xf, ep, has32, has16, ws, planes, k);
+    out[6] = k[0]; out[7] = k[1]; out[11] = k[3];
+    if (k[2]) out[9] = 1;
+    if (ep.kind == UAD_EPI_FINAL) {
+        const bool ok = on16 ? uad_conv_d_can_fuse_final(d, true, ws.floats) : uad_conv_d_can_fuse_final_f32(d, has32, ws.floats);
+        if (!ok || d.KS != 5) out[9] = 1;
+        if (ep.fin_bits && !on16) out[9] = 1;      // the exact-fp32 kernel writes the uncompressed gradient only
+    }
+}
+
+int uad_op_conv_plan(const uad_conv_desc_t* dd, int kind, int epi, int xf_flags, long long* out) {
+    if (!dd || !out) return fail(UAD_ERR_INVALID, "null argument");
+    const UadConvDesc d = to_desc(dd);
+    static float some;      // presence of an operand is all a plan reads
+    if (kind == 'F' || kind == 'D') {
+        UadEpilogue e;
+        memset(&e, 0, sizeof e);
+        const bool has_xf = (xf_flags & UAD_OP_XF_IN) != 0, fb = kind == 'F' && (xf_flags & UAD_OP_XF_FINAL_BWD);
+        if (epi == UAD_OP_EPI_BIAS) e.kind = UAD_EPI_BIAS;
+        else if (epi == UAD_OP_EPI_BWD_ACT) e.kind = UAD_EPI_BWD_ACT;
+        else if (kind == 'D' && (epi == UAD_OP_EPI_FINAL || epi == UAD_OP_EPI_FINAL_TRAIN || epi == UAD_OP_EPI_FINAL_DC)) {
+            e.kind = UAD_EPI_FINAL; e.ealpha = 0.3f;
+            if (epi == UAD_OP_EPI_FINAL_TRAIN) { e.fin_bits = reinterpret_cast<unsigned*>(&some); e.fin_dxhat = &some; }
+            if (epi == UAD_OP_EPI_FINAL_DC) e.fin_dc = &some;
+        } else return fail(UAD_ERR_INVALID, "unknown epilogue %d for kind %c", epi, kind);
+        op_plan_fd(d, kind == 'F', e, has_xf || fb, epi == UAD_OP_EPI_BIAS && !has_xf && !fb, fb, out);      // (plain: a bias launch without activation on load; `mul` is not part of the query)
+        return UAD_OK;
+    }
+    if (kind == 'W') {
+        for (int i = 0; i < 12; ++i) out[i] = 0;
+        const int planes = (op_bf16x6() && d.KS == 5) ? 3 : 2;
+        uad_conv_w_plan_query(d, op_bf16x3(), planes, false, (xf_flags & UAD_OP_XF_IN) != 0, (xf_flags & UAD_OP_XF_SMALL) != 0, op_bf16x3(), false, out);
+        out[6] = 0; out[9] = 0; out[10] = op_math(); out[11] = 0;
+        return UAD_OK;
+    }
+    return fail(UAD_ERR_INVALID, "kind must be 'F', 'D' or 'W'");
+}
+
+static int op_conv_f(const uad_conv_desc_t* d, const float* big_in, UadXform xf, const float* W, const float* bias,
+                     const float* mul, const float* add, float* small_out, void* stream) {
+    if (int rc = check_gemm_desc(d, true)) return rc;
+    const bool plain = !xf.scale && !mul, fb = xf.fb_bits != nullptr;
+    long long q[12];
+    op_plan_fd(to_desc(d), true, epi_bias(bias, mul, add), xf.scale != nullptr, plain, fb, q);
+    if (q[9]) return fail(UAD_ERR_UNSUPPORTED, "final backward on load: no F-kind spatial instance takes this launch (uad_op_conv_plan)");
+    OpPacks pk;
+    if (int rc = pack_for_op(to_desc(d), W, true, &pk, (hipStream_t)stream, plain)) { pk.release(); return rc; }
+    UadGemmWs ws;
+    if (int rc = ws_for_op(to_desc(d), true, pk.any(), &ws)) { pk.release(); (void)hipFree(ws.ptr); return rc; }
+    uad_launch_conv_f(to_desc(d), big_in, xf, W, small_out, epi_bias(bias, mul, add), (hipStream_t)stream, OP_PACK_ARGS(pk, *d, true));
+    return finish_op(pk, (hipStream_t)stream, ws.ptr);
+}
+int uad_op_conv_f(const uad_conv_desc_t* d, const float* big_in, const uad_xform_t* xf, const float* W, const float* bias,
+                  const float* mul, const float* add, float* small_out, void* stream) {
+    return op_conv_f(d, big_in, to_xf(xf), W, bias, mul, add, small_out, stream);
+}
+int uad_op_conv_f_final_bwd(const uad_conv_desc_t* d, const unsigned* bits, const float* dxhat, const float* wf, const uad_xform_t* bn, const float* W,
+                            const float* bias, const float* mul, const float* add, float* small_out, void* stream) {
+    if (!bits || !dxhat || !wf || !bn || !bn->scale) return fail(UAD_ERR_INVALID, "final backward on load needs the pattern words, d / d x_hat, the final kernel and the block's scale / shift");
+    UadXform xf = to_xf(bn);
+    xf.fb_bits = bits; xf.fb_dxhat = dxhat; xf.fb_wf = wf;
+    return op_conv_f(d, nullptr, xf, W, bias, mul, add, small_out, stream);
+}
+int uad_op_conv_d(const uad_conv_desc_t* d, const float* small_in, const uad_xform_t* xf, const float* W, const float* bias,
+                  const float* mul, const float* add, float* big_out, void* stream) {
+    if (int rc = check_gemm_desc(d, false)) return rc;
+    OpPacks pk;
+    const bool plain = !(xf && xf->scale) && !mul;
+    long long q[12];
+    op_plan_fd(to_desc(d), false, epi_bias(bias, mul, add), xf && xf->scale, plain, false, q);
+    if (q[9]) return fail(UAD_ERR_UNSUPPORTED, "conv_d: the kernel this launch would run has no form for it (uad_op_conv_plan)");
+    if (int rc = pack_for_op(to_desc(d), W, false, &pk, (hipStream_t)stream, plain)) { pk.release(); return rc; }
+    UadGemmWs ws;
+    if (int rc = ws_for_op(to_desc(d), false, pk.any(), &ws)) { pk.release(); (void)hipFree(ws.ptr); return rc; }
+    uad_launch_conv_d(to_desc(d), small_in, to_xf(xf), W, big_out, epi_bias(bias, mul, add), (hipStream_t)stream, OP_PACK_ARGS(pk, *d, false));
+    return finish_op(pk, (hipStream_t)stream, ws.ptr);
+}
+
+int uad_op_conv_d_final(const uad_conv_desc_t* dd, const float* small_in, const uad_xform_t* xf, const float* W, const float* bias, const uad_xform_t* bn,
+                        const float* wf, const float* bf, const float* x, float inv_batch, float* x_hat, float* l1, float* rec_sum,
+                        unsigned* bits, float* dxhat, float* dc, float* red, void* stream) {
+    if (int rc = check_gemm_desc(dd, false)) return rc;
+    if (!small_in || !W || !bn || !bn->scale || !bn->shift || !wf || !bf || !x || !x_hat || !rec_sum) return fail(UAD_ERR_INVALID, "conv_d_final: null argument");
+    if ((bits != nullptr) != (dxhat != nullptr) || (bits && dc) || ((bits || dc) && !red)) return fail(UAD_ERR_INVALID, "conv_d_final: forms are forward only, (bits, dxhat, red) or (dc, red)");
+    const UadConvDesc d = to_desc(dd);
+    hipStream_t st = (hipStream_t)stream;
+    UadEpilogue e;
+    memset(&e, 0, sizeof e);
+    e.kind = UAD_EPI_FINAL; e.bias = bias;
+    e.escale = bn->scale; e.eshift = bn->shift; e.ealpha = bn->alpha; e.emult = 1.f;
+    e.fin_wf = wf; e.fin_bf = bf; e.fin_x = x; e.fin_xhat = x_hat; e.fin_l1 = l1;
+    e.fin_dc = dc; e.fin_bits = bits; e.fin_dxhat = dxhat; e.fin_inv_batch = inv_batch;
+    long long q[12];
+    op_plan_fd(d, false, e, xf && xf->scale, false, false, q);
+    if (q[9]) return fail(UAD_ERR_UNSUPPORTED, "conv_d_final: no kernel with the fused final epilogue takes this launch (uad_op_conv_plan)");
+    // partial sums: one slot per 8 x 16 tile of the small map (the layout every instance writes and uad_final_blocks_per_sample counts)
+    const int T = d.N * (d.HS / 8) * (d.WS / 16), L = 3 * d.CB + 1;
+    float *recp = nullptr, *redp = nullptr;
+    HIP_TRY(hipMalloc((void**)&recp, (size_t)T * sizeof(float)));
+    if (hipMalloc((void**)&redp, (size_t)T * L * sizeof(float)) != hipSuccess) { (void)hipFree(recp); return fail(UAD_ERR_HIP, "conv_d_final: out of device memory"); }
+    e.fin_rec_partial = recp; e.fin_red_partial = redp;
+    OpPacks pk;
+    if (int rc = pack_for_op(d, W, false, &pk, st)) { pk.release(); (void)hipFree(recp); (void)hipFree(redp); return rc; }
+    UadGemmWs ws;
+    if (int rc = ws_for_op(d, false, pk.any(), &ws)) { pk.release(); (void)hipFree(ws.ptr); (void)hipFree(recp); (void)hipFree(redp); return rc; }
+    uad_launch_conv_d(d, small_in, to_xf(xf), W, nullptr, e, st, OP_PACK_ARGS(pk, *dd, false));
+    uad_launch_reduce_partials(recp, T, 1, 1.0f, rec_sum, st);
+    if (red) uad_launch_reduce_partials(redp, T, L, 1.0f, red, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    (void)hipFree(recp); (void)hipFree(redp);
+    return finish_op(pk, st, ws.ptr);
+}
+
+static int bwdact_common(bool f_type, const uad_conv_desc_t* dd, const float* in, const float* W, const float* cprev,
+                         const uad_xform_t* act, float* out, float* s1, float* s2, void* stream) {
+    if (int rc = check_gemm_desc(dd, f_type)) return rc;
+    if (!act || !act->scale) return fail(UAD_ERR_INVALID, "bwdact needs the activation scale/shift");
+    UadConvDesc d = to_desc(dd);
+    const int C = f_type ? d.CS : d.CB;
+    UadEpilogue e;
+    memset(&e, 0, sizeof e);
+    e.kind = UAD_EPI_BWD_ACT; e.cprev = cprev; e.escale = act->scale; e.eshift = act->shift; e.ealpha = act->alpha;
+    e.emult = 1.f;
+    long long q[12];
+    op_plan_fd(d, f_type, e, false, false, false, q);
+    if (q[9]) return fail(UAD_ERR_UNSUPPORTED, "bwdact: the kernel this launch would run has no form for it (uad_op_conv_plan)");
+    const int T = (int)q[4];      // column-partial tiles of the plan the launcher will make
+    hipStream_t st = (hipStream_t)stream;
+    OpPacks pk;
+    if (int rc = pack_for_op(d, W, f_type, &pk, st)) { pk.release(); return rc; }
+    UadGemmWs ws;
+    if (int rc = ws_for_op(d, f_type, pk.any(), &ws)) { pk.release(); (void)hipFree(ws.ptr); return rc; }
+    float* colpart = nullptr;
+    if (hipMalloc((void**)&colpart, (size_t)T * 2 * C * sizeof(float)) != hipSuccess) { pk.release(); (void)hipFree(ws.ptr); return fail(UAD_ERR_HIP, "bwdact: out of device memory"); }
+    e.colpart = colpart;
+    if (f_type) uad_launch_conv_f(d, in, no_xform(), W, out, e, st, OP_PACK_ARGS(pk, *dd, true));
+    else uad_launch_conv_d(d, in, no_xform(), W, out, e, st, OP_PACK_ARGS(pk, *dd, false));
+    // rstd = 1, gamma unused for dbias=null: dbeta -> s1, dgamma -> s2
+    uad_launch_bn_grad_finalize(colpart, T, C, act->scale, 1.0f, s2, s1, nullptr, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    (void)hipFree(colpart);
+    return finish_op(pk, st, ws.ptr);
+}
+int uad_op_conv_f_bwdact(const uad_conv_desc_t* d, const float* big_in, const float* W, const float* cprev,
+                         const uad_xform_t* act, float* small_out, float* s1, float* s2, void* stream) {
+    return bwdact_common(true, d, big_in, W, cprev, act, small_out, s1, s2, stream);
+}
+int uad_op_conv_d_bwdact(const uad_conv_desc_t* d, const float* small_in, const float* W, const float* cprev,
+                         const uad_xform_t* act, float* big_out, float* s1, float* s2, void* stream) {
+    return bwdact_common(false, d, small_in, W, cprev, act, big_out, s1, s2, stream);
+}
+
+int uad_op_conv_w(const uad_conv_desc_t* dd, const float* big, const uad_xform_t* xfb, const float* small_,
+                  const uad_xform_t* xfs, float* dW, void* stream) {
+    if (!dd) return fail(UAD_ERR_INVALID, "null desc");
+    if (dd->CB % 4 || dd->CS % 4) return fail(UAD_ERR_UNSUPPORTED, "channels must be multiples of 4");
+    UadConvDesc d = to_desc(dd);
+    float* partial = nullptr;
+    HIP_TRY(hipMalloc((void**)&partial, uad_conv_w_partial_floats(d) * sizeof(float)));
+    hipStream_t st = (hipStream_t)stream;
+    // bf16x6: the k5 s2 kernel's three-plane instances where w_tr_x6_takes the operand forms, the exact-fp32 k5 kernel where it does not (uad_launch_conv_w decides;
+    // the filter gradient reads no weight pack)
+    const int planes = (op_bf16x6() && d.KS == 5) ? 3 : 2;
+    uad_launch_conv_w(d, big, to_xf(xfb), small_, to_xf(xfs), dW, partial, st, op_bf16x3(), nullptr, nullptr, op_bf16x3(), false, planes);
+    HIP_TRY(hipStreamSynchronize(st));
+    hipFree(partial);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_op_conv_first_fwd(const uad_conv_desc_t* d, const float* x, const float* W, const float* bias, float* out, void* stream) {
+    if (!d || d->CS % 8 || 256 % (d->CS / 8)) return fail(UAD_ERR_UNSUPPORTED, "first conv: Cout must be a multiple of 8 dividing 2048");
+    uad_launch_conv_first_fwd(to_desc(d), x, W, bias, out, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+int uad_op_conv_first_wgrad(const uad_conv_desc_t* dd, const float* x, const float* g, float* dW, void* stream) {
+    if (!dd || !((dd->KS == 5 && (dd->CB == 1 || dd->CB == 3)) || (dd->KS == 3 && dd->CB == 1)) || 256 % dd->CS)
+        return fail(UAD_ERR_UNSUPPORTED, "first wgrad: (KS=5, Cin in {1,3}) or (KS=3, Cin=1), Cout | 256");
+    UadConvDesc d = to_desc(dd);
+    float* partial = nullptr;
+    HIP_TRY(hipMalloc((void**)&partial, uad_conv_first_wgrad_partial_floats(d) * sizeof(float)));
+    hipStream_t st = (hipStream_t)stream;
+    uad_launch_conv_first_wgrad(d, x, g, dW, partial, st);
+    HIP_TRY(hipStreamSynchronize(st));
+    hipFree(partial);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+int uad_op_adam(float* p, const float* g, float* mm, float* v, long long n, float lr_t, float beta1, float beta2, float eps,
+                float gscale, void* stream) {
+    uad_launch_adam(p, g, mm, v, (size_t)n, lr_t, beta1, beta2, eps, gscale, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+}  // extern "C"

@@ -24,12 +24,6 @@
 
 #define fail uad_fail
 
-#define RS_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
 
 constexpr int ZOOM_PAD = 12;       // scipy.ndimage._interpolation._prepad_for_spline_filter: npad of mode 'nearest'
@@ -311,13 +305,13 @@ int uad_zoom_spline3(const float* in, int n, int h, int w, int H, int W, int bou
     const double zy = H > 1 ? (double)(h - 1) / (double)(H - 1) : 1.0, zx = W > 1 ? (double)(w - 1) / (double)(W - 1) : 1.0;
     const size_t cols = (size_t)n * wp;
     hipLaunchKernelGGL(zoom_cols_kernel<PREFILTER_MIRROR>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, in, n, h, w, pad, hp, wp, z, std::pow(z, hp - 1), coef);
-    RS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const int rows = n * hp;
     hipLaunchKernelGGL(zoom_rows_kernel<PREFILTER_MIRROR>, dim3((unsigned)((rows + ZOOM_TILE - 1) / ZOOM_TILE)), dim3(ZOOM_TILE), 0, st, coef, rows, wp, z, std::pow(z, wp - 1));
-    RS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const dim3 grid((W + 63) / 64, (H + 3) / 4, n < 65535 ? n : 65535);
     hipLaunchKernelGGL(zoom_interp_kernel, grid, dim3(64, 4), 0, st, (const double*)coef, n, pad, hp, wp, H, W, zy, zx, out_kind, out);
-    RS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
@@ -333,10 +327,10 @@ int affine_prefilter(const float* in, int n, int h, int w, int pad, double* coef
     const int e = INIT == PREFILTER_REFLECT ? 0 : 1;           // zn = z^len (reflect) or z^(len-1) (mirror)
     const size_t cols = (size_t)n * wp;
     hipLaunchKernelGGL(zoom_cols_kernel<INIT>, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, st, in, n, h, w, pad, hp, wp, z, std::pow(z, hp - e), coef);
-    RS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const int rows = n * hp;
     hipLaunchKernelGGL(zoom_rows_kernel<INIT>, dim3((unsigned)((rows + ZOOM_TILE - 1) / ZOOM_TILE)), dim3(ZOOM_TILE), 0, st, coef, rows, wp, z, std::pow(z, wp - e));
-    RS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 }  // namespace
@@ -369,7 +363,7 @@ int uad_affine_spline3(const float* in, int n, int h, int w, int H, int W, const
     if (rc != UAD_OK) return rc;
     const dim3 grid((W + 15) / 16, (H + 15) / 16, n < 65535 ? n : 65535);
     hipLaunchKernelGGL(affine_interp_kernel, grid, dim3(16, 16), 0, st, (const double*)coef, n, K, pad, h, w, H, W, tab, out_kind, out);
-    RS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 

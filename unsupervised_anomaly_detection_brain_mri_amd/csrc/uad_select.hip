@@ -26,12 +26,6 @@
 
 #define fail uad_fail
 
-#define SEL_TRY(expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(UAD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
 
 constexpr int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, SEL_ROUNDS = 8;
@@ -380,12 +374,12 @@ int uad_select_quantiles(const float* in, int n_seg, long long n_per_seg, const 
     SelState* states = (SelState*)workspace;
     unsigned* counts = (unsigned*)(states + n_seg);
     // tickets and counters start every call at zero whatever the workspace held; between the passes the last arrivers keep them there
-    SEL_TRY(hipMemsetAsync(workspace, 0, need, st));
+    HIP_TRY(hipMemsetAsync(workspace, 0, need, st));
     const dim3 grid((unsigned)select_tiles((unsigned long long)n_per_seg), (unsigned)n_seg);
     for (int pass = 0; pass < 4; ++pass) {
         hipLaunchKernelGGL(select_pass_kernel<false>, grid, dim3(SEL_THREADS), 0, st, in, (unsigned long long)n_per_seg, pass, filter, qs, states, counts,
                            m_out, bracket_out, SelMask{nullptr, 0.f, 0.f, 0});
-        SEL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return UAD_OK;
 }
@@ -411,12 +405,12 @@ int uad_select_quantiles_masked(const float* in, const uint8_t* labels, long lon
     hipStream_t st = (hipStream_t)stream;
     SelState* states = (SelState*)workspace;
     unsigned* counts = (unsigned*)(states + 1);
-    SEL_TRY(hipMemsetAsync(workspace, 0, need, st));
+    HIP_TRY(hipMemsetAsync(workspace, 0, need, st));
     const dim3 grid((unsigned)select_tiles((unsigned long long)n), 1u);
     for (int pass = 0; pass < 4; ++pass) {
         hipLaunchKernelGGL(select_pass_kernel<true>, grid, dim3(SEL_THREADS), 0, st, in, (unsigned long long)n, pass, (int)UAD_SELECT_ALL, qs, states, counts,
                            m_out, bracket_out, SelMask{labels, lo, hi, class_id});
-        SEL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return UAD_OK;
 }
@@ -427,7 +421,7 @@ int uad_histogram_edges(const float* in, long long n, const float* edges, int bi
     if (bins <= 0 || bins > UAD_HISTOGRAM_MAX_BINS) return fail(UAD_ERR_INVALID, "histogram_edges: 1 .. %d bins, got %d", UAD_HISTOGRAM_MAX_BINS, bins);
     if (((uintptr_t)in & 3) != 0) return fail(UAD_ERR_INVALID, "histogram_edges: input must be 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    SEL_TRY(hipMemsetAsync(counts, 0, (size_t)bins * sizeof(long long), st));
+    HIP_TRY(hipMemsetAsync(counts, 0, (size_t)bins * sizeof(long long), st));
     if (n == 0) return UAD_OK;
     const unsigned long long chunks = ((unsigned long long)n + 3 + 3) / 4;
     unsigned long long blocks = (chunks + HE_THREADS - 1) / HE_THREADS;
@@ -435,7 +429,7 @@ int uad_histogram_edges(const float* in, long long n, const float* edges, int bi
     const size_t lds = ((size_t)((bins + 1 + 3) & ~3) + (size_t)HE_WAVES * bins) * sizeof(unsigned);
     hipLaunchKernelGGL(hist_edges_kernel, dim3((unsigned)blocks), dim3(HE_THREADS), lds, st, in, (unsigned long long)n, edges, bins,
                        (unsigned long long*)counts);
-    SEL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
@@ -447,7 +441,7 @@ int uad_clamp_scale(const float* in, long long n, float lo, float hi, float scal
     unsigned long long blocks = (items + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(clamp_scale_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, (unsigned long long)n, lo, hi, scale, out, vec);
-    SEL_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
 
