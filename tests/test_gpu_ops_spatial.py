@@ -1,6 +1,6 @@
 """GPU: every instance of the k5 s2 spatial kernels, one launch at a time, against the fp64 numpy oracle (oracle/nn.py + the epilogue written out).
 
-run_plan (csrc/uad_gemm.hip) and launch_w_tr dispatch to the instances listed in WANTED below; the whole-model tests reach them only through a training step and
+run_plan (csrc/uad_conv_plan.hip) and launch_w_tr dispatch to the instances listed in WANTED below; the whole-model tests reach them only through a training step and
 a max-norm over whole tensors.  Here each (kind, instance, epilogue form, math mode) is one test of four steps:
 
 1. plan: uad_op_conv_plan (host only) has to name the instance the case is called after -- path, splits, slab reduction, column block, D-kind generation and

@@ -1,8 +1,8 @@
 """Static VALU split by instruction class, per kernel, from the gfx950 assembly of one translation unit (the `.s` that
 `tools/kregs.py <unit>` writes to /tmp/isa/<unit>.s; the same code the shipped .so carries — same flags but -gline-tables-only).
 
-    python tools/kregs.py uad_gemm conv5_            # (re)generates /tmp/isa/uad_gemm.s
-    python tools/isa_classes.py /tmp/isa/uad_gemm.s conv5_d16s conv5_f16 conv5_w_bf16_tr [--md] [--lines N]
+    python tools/kregs.py uad_conv5_f conv5_         # (re)generates /tmp/isa/uad_conv5_f.s (one unit per kernel family: DESIGN section 24)
+    python tools/isa_classes.py /tmp/isa/uad_conv5_f.s conv5_f16 conv5_f_kernel [--md] [--lines N]
 
 Classes (VALU only; MFMA, LDS, VMEM, SALU are printed beside them):
   fp     v_fma/v_mul/v_add/v_sub/v_max/v_min/v_mac/v_pk_* on f32/f16, v_rcp/v_rsq/v_exp/v_log/v_sqrt …  (without DPP/SDWA modifiers)

@@ -1,5 +1,5 @@
-"""Static instruction census of one kernel by source line: `hipcc -O3 -gline-tables-only -S --cuda-device-only csrc/uad_gemm.hip -o gemm.s`,
-then `python tools/isa_lines.py gemm.s <kernel-name-substring> [top]`.  Attributes every instruction between the kernel's label and its
+"""Static instruction census of one kernel by source line: `hipcc -O3 -gline-tables-only -S --cuda-device-only csrc/<unit>.hip -o unit.s` (the unit that owns
+the kernel: uad_gemm.hip, uad_conv5_f / _d / _w.hip, uad_conv_k3.hip, ...), then `python tools/isa_lines.py unit.s <kernel-name-substring> [top]`.  Attributes every instruction between the kernel's label and its
 s_endpgm to the innermost `.loc` line in effect and prints per-line counts by class (MFMA / VALU / SALU / LDS / VMEM / other).  Static
 counts equal dynamic counts only for fully unrolled code; the loop structure is visible from the branch targets printed with --blocks."""
 import collections

@@ -1,6 +1,6 @@
 """Instruction census of the LOOP BODIES of one kernel (blocks the assembler comments mark `Loop Header` / `in Loop: Header=...`), VALU split by the
 classes of tools/isa_classes.py: the per-iteration (= per-tile) instruction mix, without prologue and epilogue.
-    python tools/isa_loop.py /tmp/isa/uad_gemm.s <mangled-name substring>"""
+    python tools/isa_loop.py /tmp/isa/<unit>.s <mangled-name substring>"""
 import collections
 import os
 import re

@@ -4,15 +4,9 @@
 //   tools/k3_ubench N H W CA Nn [planes]        (k3 s1 forward form)
 #include <vector>
 #include <string.h>
-#include "../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_gemm_common.h"
-
-namespace {
-struct ConvWArgs {
-    const float* big; const float* small_; float* partial; UadXform xfb, xfs; UadConvDesc d;
-    int Mtot, Kt, kper, lws, lhs; unsigned long long* dbgbuf; int npl = 2; int abl = 0;
-};
-#include "../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_convk16.inc"
-}
+// (the family's unit itself, so that the -D switches reach the kernels of uad_convk16.inc, and the planner's host-side choosers / tap lists)
+#include "../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_conv_k3.hip"
+#include "../unsupervised_anomaly_detection_brain_mri_amd/csrc/uad_conv_k3_plan.h"
 
 #define CK_(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
 
@@ -56,7 +50,7 @@ int main(int argc, char** argv) {
         wa.big = big; wa.small_ = sm; wa.partial = part; wa.d = dw; wa.Mtot = 9 * CA; wa.Kt = N * H * W; wa.lws = wa.lhs = -1; wa.npl = 2;
         hipStream_t st; CK_(hipStreamCreate(&st));
         hipEvent_t a, b; CK_(hipEventCreate(&a)); CK_(hipEventCreate(&b));
-        auto go = [&]() { if (S == 1) { if (k3.ncb == 2) launch_convk_w16<1, 2>(wa, k3, st); else launch_convk_w16<1, 1>(wa, k3, st); } else launch_convk_w16<2, 1>(wa, k3, st); };
+        auto go = [&]() { uad_k3_launch_w(wa, k3, S, k3.ncb, st); };
         for (int i = 0; i < 3; ++i) go();
         CK_(hipStreamSynchronize(st));
         const int reps = 30;

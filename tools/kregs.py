@@ -1,6 +1,6 @@
 """Register / LDS / scratch table of the kernels in one translation unit: compiles csrc/<file>.hip to gfx950 assembly
 (-gline-tables-only, so tools/isa_lines.py can read the same file) and prints the .amdhsa descriptors of the kernels whose
-mangled name contains a key.  `python tools/kregs.py uad_gemm conv5_d16s [more keys]` -> /tmp/isa/uad_gemm.s"""
+mangled name contains a key.  `python tools/kregs.py uad_gemm_d16s conv5_d16s [more keys]` -> /tmp/isa/uad_gemm_d16s.s (the unit that owns the kernel: DESIGN section 24)"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 unit = sys.argv[1]; keys = sys.argv[2:] or ['']

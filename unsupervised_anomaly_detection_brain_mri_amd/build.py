@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, 'libuad_hip.so')
-SOURCES = ['uad_gemm.hip', 'uad_gemm_d16s.hip', 'uad_gemm_d16s3.hip', 'uad_misc.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_hist.hip', 'uad_flow.hip', 'uad_resize.hip', 'uad_cc.hip', 'uad_crops.hip', 'uad_batch.hip', 'uad_render.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_ops.hip', 'uad_allreduce.hip']
+SOURCES = ['uad_gemm_d16s3.hip', 'uad_gemm_d16s.hip', 'uad_conv_k3.hip', 'uad_conv5_f.hip', 'uad_conv5_d.hip', 'uad_conv5_w.hip', 'uad_gemm.hip', 'uad_conv_plan.hip', 'uad_misc.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_hist.hip', 'uad_flow.hip', 'uad_resize.hip', 'uad_cc.hip', 'uad_crops.hip', 'uad_batch.hip', 'uad_render.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_ops.hip', 'uad_allreduce.hip']
 ARCH = 'gfx950'
 # per-file flags.  uad_flow.hip must return the bits of utils/curvature_flow.py, uad_resize.hip those of utils/resize.py and uad_render.hip those of
 # utils/render.py: no multiply-add may be fused, in host or device code; uad_hist.hip's centred squares are added as tests/native/hist_emu.cpp adds them;
@@ -41,7 +41,8 @@ def build(force=False, verbose=False):
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, 'uad_kernels.h'), os.path.join(CSRC, 'uad_handle.h'), os.path.join(CSRC, 'uad_allreduce.h'), os.path.join(ROOT, 'include', 'uad_hip.h'), os.path.join(CSRC, 'uad_gan_kernels.inc'),
                os.path.join(CSRC, 'uad_gan_create.inc'), os.path.join(CSRC, 'uad_conv16s.inc'), os.path.join(CSRC, 'uad_convk16.inc'),
-               os.path.join(CSRC, 'uad_conv5_f32.inc'), os.path.join(CSRC, 'uad_conv5_f32w.inc'), os.path.join(CSRC, 'uad_gemm_common.h'), os.path.join(CSRC, 'uad_gemm_d16s_body.inc')]      # the .inc files are textual parts of uad_gan.hip
+               os.path.join(CSRC, 'uad_gemm_common.h'), os.path.join(CSRC, 'uad_conv_launch.h'), os.path.join(CSRC, 'uad_conv_k3_plan.h'), os.path.join(CSRC, 'uad_gemm_d16s_body.inc')]
+    # (the .inc files are textual parts of a unit: uad_gan_*.inc of uad_gan.hip, uad_conv16s.inc / uad_gemm_d16s_body.inc of uad_gemm_d16s*.hip, uad_convk16.inc of uad_conv_k3.hip)
     objs = []
     # hidden visibility: the library exports exactly the functions include/uad_hip.h declares (its visibility push), none of the C++ launch layer
     flags = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-fvisibility=hidden', '-fvisibility-inlines-hidden', '-Wno-unused-value', '-Wno-unused-result']
@@ -55,7 +56,7 @@ def build(force=False, verbose=False):
                 print(' '.join(cmd), file=sys.stderr)
             jobs.append(cmd)
         objs.append(obj)
-    # the translation units are independent: compile them side by side (uad_gemm.hip alone takes minutes)
+    # the translation units are independent: compile them side by side (the lane = pixel units uad_gemm_d16s*.hip alone take minutes: they are started first)
     procs = [subprocess.Popen(cmd) for cmd in jobs]
     failed = [cmd for cmd, pr in zip(jobs, procs) if pr.wait() != 0]
     if failed:

@@ -593,7 +593,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) __attribute__((amdgpu_waves_pe
 }
 
 template <int TH, int TW, int CST, int WGM, int WGN, int MF, int EPI, bool XF, bool GRAD, int NPL>
-void launch_conv5_d16s_e(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
+void launch_conv5_d16s_e(const ConvGemmArgs& a, dim3 grid, bool any_order, hipStream_t st) {
     constexpr size_t lds = conv5_d16s_lds_bytes<TH, TW, CST, WGM, WGN, NPL>(EPI);
     static bool attr_set = false;
     if (!attr_set) {
@@ -601,7 +601,7 @@ void launch_conv5_d16s_e(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    UAD_SPATIAL_LAUNCH((conv5_d16s_kernel<TH, TW, CST, WGM, WGN, MF, EPI, XF, GRAD, NPL>), grid, dim3(64 * WGM * WGN), lds, st, a);
+    UAD_SPATIAL_LAUNCH(any_order, (conv5_d16s_kernel<TH, TW, CST, WGM, WGN, MF, EPI, XF, GRAD, NPL>), grid, dim3(64 * WGM * WGN), lds, st, a);
 }
 // true when the lane = pixel kernel takes this launch (else: conv5_d16_kernel).  Instantiated (each instance is a fully unrolled 25 x CST / 32-unit kernel;
 // round 6 halved the list for compile time): plain epilogue WITH activation-on-load (every decoder block of the model reads its producer's BN), backward
@@ -622,8 +622,8 @@ inline bool conv5_d16s_t16(const ConvGemmArgs& a) {
     return t16 && a.ep.fin_bits && a.nsplit == 1 && a.d.HS % 16 == 0;
 }
 template <int TH, int TW, int CST, int WGM, int WGN, int MF, int NPL>
-void launch_conv5_d16s_n(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
-    if (a.ep.kind == UAD_EPI_BWD_ACT) launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_BWD_ACT, false, false, NPL>(a, grid, st);
+void launch_conv5_d16s_n(const ConvGemmArgs& a, dim3 grid, bool any_order, hipStream_t st) {
+    if (a.ep.kind == UAD_EPI_BWD_ACT) launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_BWD_ACT, false, false, NPL>(a, grid, any_order, st);
     else if (a.ep.kind == UAD_EPI_FINAL) {
         if constexpr (WGN == 1) {
             // round 6 (late): the training instance of the 32-channel last block on 16 x 16 tiles, two pixel fragments per wave -- half the workgroups, a weight
@@ -631,25 +631,25 @@ void launch_conv5_d16s_n(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
             if constexpr (TH == 8 && TW == 16 && CST == 32 && WGM == 4 && MF == 1 && NPL == 2) {
                 if (conv5_d16s_t16(a)) {
                     grid.x = (a.d.HS / 16) * (a.d.WS / 16);
-                    launch_conv5_d16s_e<16, 16, 32, 4, 1, 2, UAD_EPI_FINAL, true, true, 2>(a, grid, st);
+                    launch_conv5_d16s_e<16, 16, 32, 4, 1, 2, UAD_EPI_FINAL, true, true, 2>(a, grid, any_order, st);
                     return;
                 }
             }
-            if (a.ep.fin_bits) launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_FINAL, true, true, NPL>(a, grid, st);
-            else launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_FINAL, true, false, NPL>(a, grid, st);
+            if (a.ep.fin_bits) launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_FINAL, true, true, NPL>(a, grid, any_order, st);
+            else launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_FINAL, true, false, NPL>(a, grid, any_order, st);
         }
-    } else launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_BIAS, true, false, NPL>(a, grid, st);
+    } else launch_conv5_d16s_e<TH, TW, CST, WGM, WGN, MF, UAD_EPI_BIAS, true, false, NPL>(a, grid, any_order, st);
 }
 template <int TH, int TW, int CST, int WGM, int WGN, int MF>
-void launch_conv5_d16s(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
-    launch_conv5_d16s_n<TH, TW, CST, WGM, WGN, MF, UAD_D16S_NPL>(a, grid, st);      // one plane count per translation unit (uad_gemm_d16s.hip / uad_gemm_d16s3.hip)
+void launch_conv5_d16s(const ConvGemmArgs& a, dim3 grid, bool any_order, hipStream_t st) {
+    launch_conv5_d16s_n<TH, TW, CST, WGM, WGN, MF, UAD_D16S_NPL>(a, grid, any_order, st);      // one plane count per translation unit (uad_gemm_d16s.hip / uad_gemm_d16s3.hip)
 }
 // tile 8 x 16 (32 output channels per workgroup) / 8 x 8 (64)
 template <int CST>
-void launch_conv5_d16s_bn32(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
-    launch_conv5_d16s<8, 16, CST, 4, 1, 1>(a, grid, st);       // (MF = 2 with half the waves measured slower on every layer: profiles/README.md, round 3)
+void launch_conv5_d16s_bn32(const ConvGemmArgs& a, dim3 grid, bool any_order, hipStream_t st) {
+    launch_conv5_d16s<8, 16, CST, 4, 1, 1>(a, grid, any_order, st);       // (MF = 2 with half the waves measured slower on every layer: profiles/README.md, round 3)
 }
 template <int CST>
-void launch_conv5_d16s_bn64(const ConvGemmArgs& a, dim3 grid, hipStream_t st) {
-    launch_conv5_d16s<8, 8, CST, 2, 2, 1>(a, grid, st);
+void launch_conv5_d16s_bn64(const ConvGemmArgs& a, dim3 grid, bool any_order, hipStream_t st) {
+    launch_conv5_d16s<8, 8, CST, 2, 2, 1>(a, grid, any_order, st);
 }

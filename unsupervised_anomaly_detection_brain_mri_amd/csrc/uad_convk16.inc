@@ -1,4 +1,4 @@
-// Part of uad_gemm.hip (textually included inside its anonymous namespace).
+// Part of uad_conv_k3.hip (textually included inside its anonymous namespace; argument block, choosers and tap lists: uad_conv_launch.h, uad_conv_k3_plan.h).
 //
 // Round 4: "tap-list" bf16x3 spatial kernel for the k3 contractions of the ResNet f-AnoGAN graph (models/fanogan_schlegl.py:31-55,70-94:
 // Conv2D k3 s1 / s2, Conv2DTranspose k3 s1 / s2 at 64-512 channels) -- until now on the generic per-tap-gather fp32 kernels.
@@ -24,23 +24,7 @@
 // m m' -- the dropped m l', l m', l l' are <= 2^-26 |x x'|, below fp32's own rounding -- on six 32-cycle bf16 MFMAs per K = 16 instead of eight
 // 64-cycle fp32 MFMAs (192 vs 512 matrix-pipe cycles), fp32 accumulation as the exact-fp32 kernels have it.
 
-struct ConvKArgs {
-    const float* A;               // input [N, AH, AW, CA]
-    const unsigned short* Wp16;   // hi plane of the tensor in the packed layout [tap][CA / 8][Nn][8]; the lo plane follows w16_plane elements later
-    long long w16_plane;
-    float* Out;                   // [N, OH, OW, Nn]
-    const float* bias;            // [Nn] or null
-    const float* add;             // layout of Out, or null
-    int N, AH, AW, CA;
-    int MH, MW;                   // iteration grid
-    int OH, OW, Nn;
-    int os, oy, ox;
-    int y0, x0;                   // input pixel of halo element (0, 0) for the tile at the grid origin
-    int toff[9];                  // per tap: hy * IW + hx inside the halo (IW = the instance's halo width)
-    int widx[9];                  // per tap: its index in the weight tensor
-};
-
-// (KFrag<NKS, NPL> and split_planes<NPL> live in uad_gemm.hip: the k5 kernels use them too since round 6)
+// (KFrag<NKS, NPL> and split_planes<NPL> live in uad_gemm_common.h: the k5 kernels use them too since round 6)
 #ifndef K3_ABL
 #define K3_ABL 0          // tools/k3_ubench.hip: kernel-tuning ablations (results are wrong): 1 no weight loads in the loop | 2 no LDS fragment reads | 4 no staging | 8 no MFMAs | 16 no barrier
 #endif
@@ -644,24 +628,6 @@ void launch_convk16(const ConvKArgs& a, int planes, hipStream_t st) {
     if (planes == 3) launch_convk16_p<SIN, EXT, NTAPS, 3>(a, st); else launch_convk16_p<SIN, EXT, NTAPS, 2>(a, st);
 }
 
-// true when uad_launch_conv_f / _d run this kernel for the launch (bf16x3 planes given): k3, s1 (P 1) or s2 (P 0, big = 2 x small), identity
-// activation on load, bias / addend epilogue, 32-channel contraction chunks, 64-channel output blocks, 8 x 8 position tiles
-inline bool convk16_shape_ok(const UadConvDesc& d, bool f_type);
-inline bool convk16_takes(const UadConvDesc& d, bool f_type, const UadXform& xf, const UadEpilogue& ep, const unsigned short* Wp16) {
-    if (!Wp16 || xf.scale || ep.kind != UAD_EPI_BIAS || ep.mul) return false;
-    return convk16_shape_ok(d, f_type);
-}
-inline bool convk16_shape_ok(const UadConvDesc& d, bool f_type) {
-    static const bool off = getenv("UAD_NO_K3") != nullptr;
-    if (off || (d.KS != 3 && d.KS != 1)) return false;
-    const int CA = f_type ? d.CB : d.CS, Nn = f_type ? d.CS : d.CB;
-    if (CA % 32 || Nn % 64 || d.HS % 8 || d.WS % 8) return false;
-    const int P1 = d.KS == 3 ? 1 : 0;          // TF SAME: k3 s1 pads 1 before; k3 s2 on an even size and every k1 pad 0
-    if (d.S == 1) return d.P == P1 && d.HB == d.HS && d.WB == d.WS;
-    if (d.S == 2) return d.P == 0 && d.HB == 2 * d.HS && d.WB == 2 * d.WS;
-    return false;
-}
-
 // k1 s2 transposed convolution (the generator's shortcut, models/fanogan_schlegl.py:40,47,54): only the even-even output pixels receive a
 // contraction; every other pixel of the output is bias (+ addend)
 __global__ void __launch_bounds__(256) k1s2_fill_kernel(float* __restrict__ out, const float* __restrict__ bias, const float* __restrict__ add,
@@ -675,68 +641,6 @@ __global__ void __launch_bounds__(256) k1s2_fill_kernel(float* __restrict__ out,
     float4 v = bias ? *reinterpret_cast<const float4*>(bias + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
     if (add) { const float4 q = *reinterpret_cast<const float4*>(add + i * 4); v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
     *reinterpret_cast<float4*>(out + i * 4) = v;
-}
-
-inline void run_convk16(const UadConvDesc& d, bool f_type, const float* in, float* out, const UadEpilogue& ep, const unsigned short* Wp16,
-                        long long w16_plane, int planes, hipStream_t st) {
-    ConvKArgs a;
-    memset(&a, 0, sizeof a);
-    a.A = in; a.Wp16 = Wp16; a.w16_plane = w16_plane; a.Out = out; a.bias = ep.bias; a.add = ep.add;
-    a.N = d.N;
-    if (d.KS == 1) {
-        // one tap: small(i, j) = big(S i, S j) W (F), or big(S i, S j) = small(i, j) W^T (D; S 2: the other output pixels are bias + addend)
-        a.toff[0] = 0; a.widx[0] = 0; a.y0 = a.x0 = 0; a.oy = a.ox = 0; a.MH = d.HS; a.MW = d.WS;
-        if (f_type) {
-            a.AH = d.HB; a.AW = d.WB; a.CA = d.CB; a.OH = d.HS; a.OW = d.WS; a.Nn = d.CS; a.os = 1;
-            if (d.S == 1) launch_convk16<1, 0, 1>(a, planes, st); else launch_convk16<2, 0, 1>(a, planes, st);
-        } else {
-            a.AH = d.HS; a.AW = d.WS; a.CA = d.CS; a.OH = d.HB; a.OW = d.WB; a.Nn = d.CB; a.os = d.S;
-            launch_convk16<1, 0, 1>(a, planes, st);
-            if (d.S == 2) {
-                const size_t total4 = (size_t)d.N * d.HB * d.WB * d.CB / 4;
-                hipLaunchKernelGGL(k1s2_fill_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, out, ep.bias, ep.add, d.WB, d.CB, total4);
-            }
-        }
-        return;
-    }
-    if (f_type) {
-        // small(i, j) = sum big(S i - P + ky, S j - P + kx) W[ky, kx]
-        a.AH = d.HB; a.AW = d.WB; a.CA = d.CB; a.MH = d.HS; a.MW = d.WS; a.OH = d.HS; a.OW = d.WS; a.Nn = d.CS;
-        a.os = 1; a.oy = a.ox = 0; a.y0 = a.x0 = -d.P;
-        const int IW = d.S * 7 + 3;
-        for (int t = 0; t < 9; ++t) { a.toff[t] = (t / 3) * IW + (t % 3); a.widx[t] = t; }
-        if (d.S == 1) launch_convk16<1, 2, 9>(a, planes, st); else launch_convk16<2, 2, 9>(a, planes, st);
-        return;
-    }
-    a.AH = d.HS; a.AW = d.WS; a.CA = d.CS; a.OH = d.HB; a.OW = d.WB; a.Nn = d.CB;
-    if (d.S == 1) {
-        // big(Y, X) = sum small(Y + 1 - ky, X + 1 - kx) W[ky, kx]: halo origin -1, tap (ky, kx) at halo offset (2 - ky, 2 - kx)
-        a.MH = d.HB; a.MW = d.WB; a.os = 1; a.oy = a.ox = 0; a.y0 = a.x0 = -1;
-        const int IW = 7 + 3;
-        for (int t = 0; t < 9; ++t) { a.toff[t] = (2 - t / 3) * IW + (2 - t % 3); a.widx[t] = t; }
-        launch_convk16<1, 2, 9>(a, planes, st);
-        return;
-    }
-    // S = 2: big(2 i + ky, 2 j + kx) <-> small(i, j).  Output-parity class (py, px), iteration (I, J) over the small grid writes big(2 I + py, 2 J + px):
-    // even: ky 0 from small row I (halo row 1) and ky 2 from row I - 1 (halo row 0); odd: ky 1 from row I.  Halo origin -1, one extra row / column.
-    a.MH = d.HS; a.MW = d.WS; a.os = 2; a.y0 = a.x0 = -1;
-    const int IW = 7 + 2;
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px) {
-            int nt = 0;
-            for (int ky = 0; ky < 3; ++ky) {
-                if ((ky & 1) != py) continue;
-                for (int kx = 0; kx < 3; ++kx) {
-                    if ((kx & 1) != px) continue;
-                    const int hy = ky == 2 ? 0 : 1, hx = kx == 2 ? 0 : 1;
-                    a.toff[nt] = hy * IW + hx; a.widx[nt] = ky * 3 + kx; ++nt;
-                }
-            }
-            a.oy = py; a.ox = px;
-            if (nt == 4) launch_convk16<1, 1, 4>(a, planes, st);
-            else if (nt == 2) launch_convk16<1, 1, 2>(a, planes, st);
-            else launch_convk16<1, 1, 1>(a, planes, st);
-        }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -781,7 +685,7 @@ convk_w16_kernel(const ConvWArgs a, int tiles_per_split, int total_tiles) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[k][c][r] = 0.f;
 
-    // fragments by transpose reads from PIXEL-major tiles (ds_read_b64_tr_b16, see conv5_w_bf16_tr_kernel in uad_gemm.hip): lane (i = l & 15,
+    // fragments by transpose reads from PIXEL-major tiles (ds_read_b64_tr_b16, see conv5_w_bf16_tr_kernel in uad_conv5_w.hip): lane (i = l & 15,
     // chalf = (l >> 4) & 1, lh = l >> 5) supplies the address of position 8 lh + 4 t + i / 4 of the K = 16 step, channels 16 chalf + 4 (i & 3) .. + 3
     auto tr8 = [&](const unsigned short* plane, const int addr, const int step) __attribute__((always_inline)) {
         const v4s r0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(const_cast<unsigned short*>(plane) + addr));
@@ -1071,25 +975,6 @@ constexpr size_t convk_w16_lds_bytes() {
     return (size_t)2 * IH * IH * (32 * NCB + 8) * 2 + (size_t)2 * 64 * (32 * 2 + 8) * 2;
 }
 
-struct WK3Choice { bool ok; int ncb, splits, tiles_per_split, total_tiles; };
-inline WK3Choice choose_wk3(const UadConvDesc& d) {
-    WK3Choice c{false, 0, 0, 0, 0};
-    static const bool off = getenv("UAD_NO_K3") != nullptr;
-    if (off || d.KS != 3) return c;
-    if (!((d.S == 1 && d.P == 1 && d.HB == d.HS && d.WB == d.WS) || (d.S == 2 && d.P == 0 && d.HB == 2 * d.HS && d.WB == 2 * d.WS))) return c;
-    if (d.CB % 32 || d.CS % 64 || d.HS % 8 || d.WS % 8) return c;
-    c.ncb = (d.S == 1 && d.CB % 64 == 0) ? 2 : 1;
-    c.total_tiles = d.N * (d.HS / 8) * (d.WS / 8);
-    const int blocks = (d.CB / (32 * c.ncb)) * (d.CS / 64);
-    int splits = (512 + blocks - 1) / blocks;
-    if (splits > c.total_tiles) splits = c.total_tiles;
-    if (splits < 1) splits = 1;
-    c.tiles_per_split = (c.total_tiles + splits - 1) / splits;
-    c.splits = (c.total_tiles + c.tiles_per_split - 1) / c.tiles_per_split;
-    c.ok = true;
-    return c;
-}
-
 #ifndef K3_WFORM
 #define K3_WFORM -1
 #endif
@@ -1124,3 +1009,4 @@ void launch_convk_w16(const ConvWArgs& a, const WK3Choice& c, hipStream_t st) {
     }
     hipLaunchKernelGGL((convk_w16_kernel<S, NCB>), grid, dim3(192 * NCB), lds, st, a, c.tiles_per_split, c.total_tiles);
 }
+

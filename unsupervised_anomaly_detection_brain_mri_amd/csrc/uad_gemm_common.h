@@ -1,44 +1,17 @@
-// Shared by the translation units of the contraction kernels (uad_gemm.hip, uad_gemm_d16s.hip): argument block, vector typedefs and the device helpers of
-// the split-bf16 kernels.  Everything lives in an anonymous namespace: each unit gets its own copy (round 6: the lane = pixel family -- 28 fully unrolled
-// instances -- moved into a unit of its own so that the two halves of the k5 kernels compile side by side).
+// Shared by the kernel units of the conv layer (uad_gemm.hip, uad_conv5_f / _d / _w.hip, uad_conv_k3.hip, uad_gemm_d16s*.hip): vector typedefs, the device
+// helpers of the split-bf16 kernels and the two launch macros.  The helpers live in an anonymous namespace: each unit gets its own copy.  The argument
+// blocks and the launch functions the planner calls are in uad_conv_launch.h; the planner itself (uad_conv_plan.hip) does not include this file.
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include "uad_kernels.h"
+#include "uad_conv_launch.h"
 #include <stdio.h>
 #include <stdlib.h>
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-#define KIND_F 0
-#define KIND_D 1
-
 namespace {
-
-struct ConvGemmArgs {
-    const float* A;
-    const float* W;
-    const float* Wp;   // k-quad-interleaved copy of W for the spatial kernels (uad_launch_pack_weights)
-    const unsigned short* Wp16;   // bf16 hi|lo planes, k-octet-interleaved (bf16x3 math mode)
-    long long w16_plane;          // elements per plane
-    float* Out;
-    UadXform xf;
-    UadEpilogue ep;
-    UadConvDesc d;
-    int M;         // N*HS*WS rows (small-image positions)
-    int CA;        // channels of the A operand (contraction per tap)
-    int Nn;        // output channels
-    int lws, lhs;  // log2(WS), log2(HS) or -1 when not a power of two
-    int nsplit;    // split-K factor (>1: raw partial tiles go to Out + split*out_elems, see splitk_epilogue_kernel)
-    long long out_elems;
-    unsigned* sk_counter;   // split-K with in-kernel reduction: arrival counters, one per (spatial tile, column block); null = splitk_epilogue_kernel
-    float* out_final;       // ... and the real output (Out points at the slabs)
-    unsigned long long* dbgbuf;   // per-phase clock stamps of a few workgroups (UAD_DBG & 8)
-    int dbg;       // ablation switches for kernel tuning (UAD_DBG): 1 = no epilogue stores, 2 = no MFMA loop, 4 = no staging
-    int math16;    // generic kernel: bf16x3 products (conv_gemm16_kernel) where the tile shape allows
-    int npl = 2;   // bf16 planes behind Wp16 (2: bf16x3, 3: bf16x6 -- the F-kind and lane = pixel spatial kernels only)
-};
 
 __device__ __forceinline__ void decode_pos(int m, int HS, int WS, int lhs, int lws, int& n, int& i, int& j) {
     if (lws >= 0 && lhs >= 0) {
@@ -199,17 +172,52 @@ constexpr TapOrderD make_tap_order_d() {
 }
 constexpr TapOrderD kTapOrderD = make_tap_order_d();
 
-// Launches without the AQL barrier bit (hipExtAnyOrderLaunch): see uad_gemm.hip.  One flag per host thread and translation unit, consumed by the next launch.
-static thread_local bool g_any_order_next = false;      // (per host thread: another thread's launch must not consume it)
-static thread_local bool g_any_order_w_next = false;      // ... the same for the next channel-major filter-gradient launch (the first one of a backward, behind loss.finalize)
-#define UAD_W_LAUNCH(kern, grid, block, lds, st, ...)                                                                       \
+// fragments and the common epilogue of the k5 s2 kernels that keep one 32x32 accumulator fragment per parity class (conv5_f_kernel, conv5_d_kernel, conv5_bf16_kernel)
+template <int NKK>
+struct BFragF { float v[NKK][4]; };
+template <int NKK>
+struct BFragD { float4 v[NKK]; };
+
+// common epilogue for one 32x32 accumulator fragment whose 16 row offsets are known
+template <int KIND_UNUSED>
+__device__ __forceinline__ void epilogue_frag(const ConvGemmArgs& a, const v16f& acc, const size_t (&obase)[16],
+                                              bool colok, int colc, float c_a, float c_b, float& s1, float& s2) {
+    if (a.ep.kind != UAD_EPI_BWD_ACT) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (!colok) continue;
+            const size_t off = obase[r] + colc;
+            float v = acc[r] + c_a;
+            if (a.ep.mul) v *= a.ep.mul[off];
+            if (a.ep.add) v += a.ep.add[off];
+            a.Out[off] = v;
+        }
+    } else {
+        float cp[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cp[r] = a.ep.cprev[colok ? (obase[r] + colc) : 0];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float c = cp[r];
+            const float bn = fmaf(c_a, c, c_b);
+            float dbn = bn > 0.f ? acc[r] : acc[r] * a.ep.ealpha;
+            dbn = colok ? dbn : 0.f;
+            if (colok) a.Out[obase[r] + colc] = dbn * c_a;
+            s1 += dbn;
+            s2 = fmaf(dbn, c, s2);
+        }
+    }
+}
+
+// any_order: the launch goes out without the AQL barrier bit (hipExtAnyOrderLaunch; the request is the planner's: uad_conv_plan.hip)
+#define UAD_W_LAUNCH(any_order, kern, grid, block, lds, st, ...)                                                            \
     do {                                                                                                                    \
-        if (g_any_order_w_next) { g_any_order_w_next = false; hipExtLaunchKernelGGL(kern, grid, block, lds, st, nullptr, nullptr, 1u, __VA_ARGS__); } \
+        if (any_order) hipExtLaunchKernelGGL(kern, grid, block, lds, st, nullptr, nullptr, 1u, __VA_ARGS__);                \
         else hipLaunchKernelGGL(kern, grid, block, lds, st, __VA_ARGS__);                                                   \
     } while (0)
-#define UAD_SPATIAL_LAUNCH(kern, grid, block, lds, st, arg)                                                                 \
+#define UAD_SPATIAL_LAUNCH(any_order, kern, grid, block, lds, st, arg)                                                      \
     do {                                                                                                                    \
-        if (g_any_order_next) { g_any_order_next = false; hipExtLaunchKernelGGL(kern, grid, block, lds, st, nullptr, nullptr, 1u, arg); } \
+        if (any_order) hipExtLaunchKernelGGL(kern, grid, block, lds, st, nullptr, nullptr, 1u, arg);                        \
         else hipLaunchKernelGGL(kern, grid, block, lds, st, arg);                                                           \
     } while (0)
 

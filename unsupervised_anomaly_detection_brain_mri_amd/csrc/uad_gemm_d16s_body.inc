@@ -9,19 +9,15 @@ namespace {
 #define UAD_D16S_CAT2(a, b) a##b
 #define UAD_D16S_CAT(a, b) UAD_D16S_CAT2(a, b)
 
-void UAD_D16S_CAT(uad_d16s_launch_v, UAD_D16S_NPL)(const void* conv_gemm_args, unsigned gx, unsigned gy, unsigned gz, int bn, int cst, bool any_order, hipStream_t st) {
-    const ConvGemmArgs& a = *static_cast<const ConvGemmArgs*>(conv_gemm_args);
-    const dim3 grid(gx, gy, gz);
-    g_any_order_next = any_order;
+void UAD_D16S_CAT(uad_d16s_launch_v, UAD_D16S_NPL)(const ConvGemmArgs& a, dim3 grid, int bn, int cst, bool any_order, hipStream_t st) {
     if (bn == 64) {
-        if (cst == 128) launch_conv5_d16s_bn64<128>(a, grid, st);
-        else if (cst == 64) launch_conv5_d16s_bn64<64>(a, grid, st);
-        else if (cst == 32) launch_conv5_d16s_bn64<32>(a, grid, st);
+        if (cst == 128) launch_conv5_d16s_bn64<128>(a, grid, any_order, st);
+        else if (cst == 64) launch_conv5_d16s_bn64<64>(a, grid, any_order, st);
+        else if (cst == 32) launch_conv5_d16s_bn64<32>(a, grid, any_order, st);
         else { fprintf(stderr, "uad: no lane = pixel instance for a %d-channel range\n", cst); abort(); }
     } else {
-        if (cst == 64) launch_conv5_d16s_bn32<64>(a, grid, st);
-        else if (cst == 32) launch_conv5_d16s_bn32<32>(a, grid, st);
+        if (cst == 64) launch_conv5_d16s_bn32<64>(a, grid, any_order, st);
+        else if (cst == 32) launch_conv5_d16s_bn32<32>(a, grid, any_order, st);
         else { fprintf(stderr, "uad: no lane = pixel instance for a %d-channel range\n", cst); abort(); }
     }
-    g_any_order_next = false;
 }

@@ -5,7 +5,7 @@
 //   * deterministic reduction of the head weight gradients (outer products over all locations);
 //   * the total-variation restore term's gradient w.r.t. the reconstruction.
 // These are tiny next to the trunk (<= 0.1 % of the FLOPs): plain fp32 VALU code, LDS for the per-location vectors,
-// no atomics.  Everything heavy (encoder / decoder k5 s2 convs) runs in uad_gemm.hip.
+// no atomics.  Everything heavy (encoder / decoder k5 s2 convs) runs in the conv layer (uad_conv_plan.hip and its kernel units).
 #include "uad_kernels.h"
 
 namespace {

@@ -129,9 +129,9 @@ bool uad_conv_f_supports_final_bwd(const UadConvDesc& d, bool have_pack16, size_
 int uad_conv_d_tiles(const UadConvDesc& d, bool have_pack = true, size_t ws_floats = 0, int ncounters = 0, int planes16 = 2);
 // workspace floats the split-K path would like for this op (0 = it would not split)
 size_t uad_conv_ws_floats(const UadConvDesc& d, bool f_type, bool have_pack);
-// tests (uad_debug_plan): the launch plan of uad_launch_conv_f / _d / _w as ten integers (fields: uad_gemm.hip, include/uad_hip.h)
+// tests (uad_debug_plan): the launch plan of uad_launch_conv_f / _d / _w as ten integers (fields: uad_conv_plan.hip, include/uad_hip.h)
 void uad_conv_plan_query(const UadConvDesc& d, bool f_type, bool have_pack, size_t ws_floats, int ncounters, int planes16, bool inst_ok, long long* out);      // inst_ok: D kind, the epilogue form has a three-plane instance
-// ... and the kernel generation of a D-kind k5 s2 spatial launch with these operands (uad_gemm.hip: run_plan).  out3: 0 generation (0: no spatial launch), 1 channel
+// ... and the kernel generation of a D-kind k5 s2 spatial launch with these operands (uad_conv_plan.hip: run_plan).  out3: 0 generation (0: no spatial launch), 1 channel
 // range a workgroup stages (`cst`; bf16 planes only), 2 the launch would abort(), 3 tile height of a fused final (16 | 8; 0: another epilogue)
 enum { UAD_DGEN_LANE_PIXEL = 1,      // conv5_d16s_kernel (uad_conv16s.inc), two or three planes
        UAD_DGEN_CLASS_SEQ = 2,       // conv5_d16_kernel: whole channel range in LDS, parity classes in sequence

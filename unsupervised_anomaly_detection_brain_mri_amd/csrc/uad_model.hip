@@ -229,7 +229,7 @@ UadBottWgradArgs bott_wgrad_args(uad_model* m, const UadBottArgs& ba, int n) {
 
 }  // namespace
 
-void uad_conv_any_order_next(bool on);      // uad_gemm.hip: the next spatial F / D launch (filter-gradient launch) leaves the AQL barrier bit clear
+void uad_conv_any_order_next(bool on);      // uad_conv_plan.hip: the next spatial F / D launch (filter-gradient launch) leaves the AQL barrier bit clear
 void uad_conv_w_any_order_next(bool on);
 
 extern "C" {

@@ -1,6 +1,6 @@
 // The part of the C-ABI (include/uad_hip.h) that takes no model handle: the library's error message and version, the stand-alone device ops
 // (residual, counter-based random fill, clock probe, slice / mask gathers), the op-level entry points uad_op_* that run ONE launch of the
-// kernels of uad_gemm.hip / uad_misc.hip on caller-supplied tensors (weight packs and workspace built on the fly, synchronous: tests and
+// kernels of the conv layer (uad_conv_plan.hip and its kernel units) / uad_misc.hip on caller-supplied tensors (weight packs and workspace built on the fly, synchronous: tests and
 // tools), and the k3 kernel's in-kernel profile switch.  Host-only: no kernel is defined here.
 #include <stdarg.h>
 #include <stdio.h>
