@@ -733,6 +733,18 @@ int uad_op_conv_first_fwd(const uad_conv_desc_t* d, const float* x, const float*
 int uad_op_conv_first_wgrad(const uad_conv_desc_t* d, const float* x, const float* g, float* dW, void* stream);
 int uad_op_adam(float* p, const float* g, float* m, float* v, long long n, float lr_t, float beta1, float beta2,
                 float eps, float gscale, void* stream);
+/* A layer's parameter-gradient tail as the train step's side stream runs it.  Parts (one whose input pointer is null is left out):
+ *   slabs[S][L] -> dW[L] (fixed-order sum);  colpart[T][2][C] -> dbeta = S1, dgamma = rstd S2, dbias = gamma rstd S1 (null outputs skipped);
+ *   fin_partial[fin_T][3 fin_C + 1] = rows of {dwf[fin_C], S1[fin_C], S2[fin_C], dbf} -> dwf, dbf and fin_dbeta / fin_dgamma / fin_dbias as above.
+ * fused = 1: one launch (C <= 512, fin_C <= 64); fused = 0: the separate launches (fin_red: 3 fin_C + 1 floats of scratch for them).  Both give the same bits.
+ * scratch: uad_op_grad_finish_scratch_floats() floats, zero before the first call, reusable by later calls on the same stream.  Asynchronous on `stream`. */
+typedef struct {
+    const float* slabs; int S, L; float* dW;
+    const float* colpart; int T, C; const float* gamma; float rstd; float *dgamma, *dbeta, *dbias;
+    const float* fin_partial; int fin_T, fin_C; const float* fin_gamma; float *dwf, *dbf, *fin_dgamma, *fin_dbeta, *fin_dbias, *fin_red;
+} uad_grad_finish_t;
+long long uad_op_grad_finish_scratch_floats(void);
+int uad_op_grad_finish(const uad_grad_finish_t* a, int fused, float* scratch, void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -75,6 +75,15 @@ class UadXform(C.Structure):
     _fields_ = [('scale', C.c_void_p), ('shift', C.c_void_p), ('alpha', C.c_float)]
 
 
+class UadGradFinish(C.Structure):
+    _fields_ = [('slabs', C.c_void_p), ('S', C.c_int), ('L', C.c_int), ('dW', C.c_void_p),
+                ('colpart', C.c_void_p), ('T', C.c_int), ('C', C.c_int), ('gamma', C.c_void_p), ('rstd', C.c_float),
+                ('dgamma', C.c_void_p), ('dbeta', C.c_void_p), ('dbias', C.c_void_p),
+                ('fin_partial', C.c_void_p), ('fin_T', C.c_int), ('fin_C', C.c_int), ('fin_gamma', C.c_void_p),
+                ('dwf', C.c_void_p), ('dbf', C.c_void_p), ('fin_dgamma', C.c_void_p), ('fin_dbeta', C.c_void_p), ('fin_dbias', C.c_void_p),
+                ('fin_red', C.c_void_p)]
+
+
 # every symbol include/uad_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'uad_last_error': (C.c_char_p, []),
@@ -207,6 +216,8 @@ SYMBOLS = {
     'uad_op_conv_first_wgrad': (C.c_int, [C.POINTER(UadConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'uad_op_adam': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float,
                               C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'uad_op_grad_finish_scratch_floats': (C.c_longlong, []),
+    'uad_op_grad_finish': (C.c_int, [C.POINTER(UadGradFinish), C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -492,6 +492,12 @@ void uad_launch_conv_w_reduce(const UadConvDesc& d, float* dW, float* partial, h
     const int splits = w5.ok ? w5.splits : choose_w(d).splits;
     if (splits > 1) uad_launch_reduce_partials(partial, splits, d.KS * d.KS * d.CB * d.CS, 1.0f, dW, st);
 }
+void uad_launch_conv_w_finish(const UadConvDesc& d, float* dW, float* partial, bool math_bf16x3, UadGradFinish a, hipStream_t st) {
+    const W5Choice w5 = choose_w5(d, math_bf16x3);
+    const int splits = w5.ok ? w5.splits : choose_w(d).splits;
+    a.partial = splits > 1 ? partial : nullptr; a.S = splits > 1 ? splits : 0; a.L = d.KS * d.KS * d.CB * d.CS; a.dW = dW;
+    uad_launch_grad_finish(a, st);
+}
 
 // tests (uad_debug_plan): what uad_launch_conv_w would run.  out[10]: 0 kernel (0 generic | 1 k5 s2 tile kernel, choose_w5 | 2 k3 tap-list kernel), 1 splits,
 // 2 the last split is short, 3 32-channel cs blocks per workgroup (k5: 1 | 2; else 0), 4 work units (k5 / k3: 8 x 8 output tiles; generic: 32-position K steps),

@@ -163,6 +163,23 @@ size_t uad_bn_grad_finalize_scratch_floats(int C);
 // red[3C+1] = {dwf[C], S1[C], S2[C], dbf} (already summed over the tiles) -> final conv kernel / bias gradients + the last block's BN / bias gradients
 void uad_launch_final_gradfin(const float* red, int C, const float* gamma, float rstd, float* dwf, float* dbf, float* dgamma, float* dbeta,
                               float* dbias, hipStream_t st);
+// One layer's parameter-gradient tail in ONE launch: the slab sum of uad_launch_reduce_partials (scale 1; same form and summation order: dW has the same bits), the
+// BN / bias finalize of uad_launch_bn_grad_finalize, and for the last decoder block the column sum of the fused loss epilogue's partials + uad_launch_final_gradfin,
+// in workgroups of their own at the lowest indices (512 threads; last-arriver through `scratch`, no workgroup waits for another; same bits as the launches they replace).
+// A part whose input pointer is null is left out.  scratch: uad_grad_finish_scratch_floats() zero-initialised floats, one per stream (a prefix of it is
+// uad_launch_bn_grad_finalize's scratch in the same layout: one buffer serves both).  Needs C <= 512 and fin_C <= 64 (uad_grad_finish_takes).
+struct UadGradFinish {
+    const float* partial; int S, L; float* dW;                                                                          // slabs [S][L] -> dW[L]
+    const float* colpart; int T, C; const float* gamma; float rstd; float *dgamma, *dbeta, *dbias;                     // colpart[T][2][C]
+    const float* fin_partial; int fin_T, fin_C; const float* fin_gamma; float *dwf, *dbf, *fin_dgamma, *fin_dbeta, *fin_dbias;      // fin_partial[fin_T][3 fin_C + 1]
+    float* scratch;
+    int nfin, nbn, NB;      // (filled by the launcher: workgroups of the final / BN part, tile ranges of the BN part)
+};
+bool uad_grad_finish_takes(int C, int fin_C);
+size_t uad_grad_finish_scratch_floats();
+void uad_launch_grad_finish(const UadGradFinish& a, hipStream_t st);
+// ... with the slab part taken from the plan of a uad_launch_conv_w(d, ..., math_bf16x3, ..., defer_reduce = true) call (none when that launch did not split)
+void uad_launch_conv_w_finish(const UadConvDesc& d, float* dW, float* partial, bool math_bf16x3, UadGradFinish a, hipStream_t st);
 // out[c] = sum_rows g[row][c]
 // scratch: kUadColsumScratchFloats floats (what every handle allocates; the row chunks of a sum are capped so that their partials fit it)
 constexpr size_t kUadColsumScratchFloats = 64 * 1024;

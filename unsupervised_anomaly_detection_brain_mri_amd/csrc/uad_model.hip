@@ -418,7 +418,7 @@ int uad_create(const uad_config_t* cfg, uad_model_t** out) {
         *m->bott_err_host = 0u;
         if (hipHostGetDevicePointer((void**)&m->bott_err_dev, m->bott_err_host, 0) != hipSuccess) m->bott_err_dev = nullptr;
     }
-    ALLOC(m->bnfin_scratch, uad_bn_grad_finalize_scratch_floats(512));
+    ALLOC(m->bnfin_scratch, uad_grad_finish_scratch_floats());      // (>= uad_bn_grad_finalize_scratch_floats(512), same layout)
     ALLOC(m->bott_wpart, NB * 4 * (2 * (size_t)m->cenc * m->cmid + m->cmid));
     // column-partial scratch: worst case 64-row tiles
     size_t cp = 0;
@@ -902,6 +902,21 @@ static void edge(uad_model* m, hipStream_t from, hipStream_t to) {
 // the side stream joined into the caller's stream: everything the handle has enqueued so far is complete in the caller's stream order
 static void join_side(uad_model* m, hipStream_t st) { edge(m, m->side, st); m->joined = true; }
 
+// a k5 layer's side work as one uad_launch_grad_finish launch (bf16 slabs, widths it takes); UAD_NO_SIDE_FUSE: the separate launches
+static bool side_fuse(const uad_model* m, int C, int fin_C) {
+    static const bool on = getenv("UAD_NO_SIDE_FUSE") == nullptr;
+    return on && bf_mode(m) && uad_grad_finish_takes(C, fin_C);
+}
+// the BN / bias finalize part of that launch: colpart[T][2][C] -> gradients of (gamma, beta, bias) at these offsets (bias < 0: none)
+static UadGradFinish bn_finish(uad_model* m, const float* cp, int T, int C, long long gamma, long long beta, long long bias) {
+    UadGradFinish f;
+    memset(&f, 0, sizeof f);
+    f.colpart = cp; f.T = T; f.C = C; f.gamma = P(m, gamma); f.rstd = 1.0f / sqrtf(1.0f + kBnEps);
+    f.dgamma = Gr(m, gamma); f.dbeta = Gr(m, beta); f.dbias = bias >= 0 ? Gr(m, bias) : nullptr;
+    f.scratch = m->bnfin_scratch;
+    return f;
+}
+
 static int backward_decoder(uad_model* m, hipStream_t st, bool join_now) {
     const int n = m->last_n;
     const float rstd = 1.0f / sqrtf(1.0f + kBnEps);
@@ -945,7 +960,23 @@ static int backward_decoder(uad_model* m, hipStream_t st, bool join_now) {
           uad_conv_any_order_next(false); }    // (a launch that did not take a spatial kernel must not leave the request to a later one)
         // ONE edge per layer: its filter-gradient slabs and column partials are ready.  Without parameter gradients (restoration, anomaly maps) nothing runs on SIDE and the
         // event record -- a marker packet with the barrier bit on the MAIN queue -- is skipped: -2.3 % per restoration iteration.  (Releasing the side work of SEVERAL layers behind
-        // one edge was measured too, round 6: 0.808 -> 0.817 / 0.839 / 0.848 ms per VAE step at 2 / 3 / 4 layers per edge -- the side stream falls behind; one edge per layer stays.)
+        // one edge was measured too, round 6: 0.808 -> 0.817 / 0.839 / 0.848 ms per VAE step at 2 / 3 / 4 layers per edge -- the side stream falls behind; one edge per layer stays.
+        // Re-measured with the one-launch side work below, two layers per edge: 0.7982 -> 0.8016 ms, profiles/r20_side_fuse.md.)
+        // Fused side chain: the slab sum, the BN / bias finalize and (last block) the fused-final sums + their finalize are ONE launch behind the edge
+        // (uad_launch_grad_finish; same bits).  UAD_NO_SIDE_FUSE, exact-fp32 slabs and layers it does not take: the separate launches below.
+        if (pg && side_fuse(m, d.CS, last ? C : 0)) {
+            UadGradFinish f = bn_finish(m, cp, uad_conv_f_tiles(d, true, m->ws.floats, sk_counters(m), planes_of(m)), d.CS, ig, ib, ibias);
+            UadGradFinish ff = f;
+            ff.colpart = nullptr; ff.fin_partial = m->red_partial; ff.fin_T = T; ff.fin_C = C; ff.fin_gamma = P(m, DL.gamma);
+            ff.dwf = Gr(m, m->fw); ff.dbf = Gr(m, m->fb); ff.fin_dgamma = Gr(m, DL.gamma); ff.fin_dbeta = Gr(m, DL.beta); ff.fin_dbias = Gr(m, DL.b);
+            if (last && !m->prof_on) { ff.colpart = f.colpart; f = ff; }      // (profiling: the final part is a launch of its own under its tag)
+            edge(m, st, sd);
+            if (last && m->prof_on) { PROF_ON("final.gradfin", sd); ff.partial = nullptr; uad_launch_grad_finish(ff, sd); }
+            PROF_ON("bn.gradfin", sd);
+            uad_launch_conv_w_finish(d, Gr(m, m->dec[i].w), m->wp_slot[i], bf, f, sd);
+            float* tsw = g; g = gn; gn = tsw;
+            continue;
+        }
         if (pg) edge(m, st, sd);
         if (pg && last) {
             // final conv kernel/bias grads + BN grads of the last block from the fused loss kernel's partials (forward results; riding on
@@ -1149,11 +1180,24 @@ static int backward_encoder(uad_model* m, hipStream_t st, int part, bool defer =
         // filter gradient instead of after them; the block gives up the any-order overlap of its two kernels for it.  UAD_NO_TAIL_SPLIT: one edge behind both.
         static const bool tail_split_on = getenv("UAD_NO_TAIL_SPLIT") == nullptr;
         const bool tail_split = tail_split_on && pg && part != 1 && i == i_last && !m->prof_on;
-        if (tail_split) { edge(m, st, sd); PROF_ON("bn.gradfin", sd); uad_launch_conv_w_reduce(d, Gr(m, m->enc[i].w), m->wp_slot[8 + (i & 7)], sd, bf); }
+        const bool fuse = pg && side_fuse(m, d.CB, 0);      // (backward_decoder)
+        if (tail_split) {
+            edge(m, st, sd); PROF_ON("bn.gradfin", sd);
+            uad_launch_conv_w_reduce(d, Gr(m, m->enc[i].w), m->wp_slot[8 + (i & 7)], sd, bf);
+        }
         { static const bool anyo = getenv("UAD_NO_ANYORDER") == nullptr; if (anyo && pg) uad_conv_any_order_next(true); }
         { PROF(kEncD[i & 7]); UadEpilogue e = epi_bwd(m, PL.c, PL.gamma, PL.beta, kLrelu); e.colpart = cp;
           uad_launch_conv_d(d, g, no_xform(), P(m, m->enc[i].w), gn, e, st, PKD(m, m->enc[i].w), m->ws, PK16D(m, m->enc[i].w), PLANE(m->enc[i]), false, planes_of(m));
           uad_conv_any_order_next(false); }
+        if (fuse) {
+            const UadGradFinish f = bn_finish(m, cp, uad_conv_d_tiles(d, true, m->ws.floats, sk_counters(m), planes_of(m)), d.CB, PL.gamma, PL.beta, PL.b);
+            edge(m, st, sd);
+            PROF_ON("bn.gradfin", sd);
+            if (tail_split) uad_launch_grad_finish(f, sd);      // (its slabs were summed behind the early edge)
+            else uad_launch_conv_w_finish(d, Gr(m, m->enc[i].w), m->wp_slot[8 + (i & 7)], bf, f, sd);
+            float* tsw = g; g = gn; gn = tsw;
+            continue;
+        }
         if (pg) edge(m, st, sd);
         if (pg) { PROF_ON("bn.gradfin", sd); if (!tail_split) uad_launch_conv_w_reduce(d, Gr(m, m->enc[i].w), m->wp_slot[8 + (i & 7)], sd, bf);
                   uad_launch_bn_grad_finalize(cp, uad_conv_d_tiles(d, true, m->ws.floats, sk_counters(m), planes_of(m)), d.CB, P(m, PL.gamma), rstd, Gr(m, PL.gamma),

@@ -372,4 +372,33 @@ int uad_op_adam(float* p, const float* g, float* mm, float* v, long long n, floa
     return UAD_OK;
 }
 
+long long uad_op_grad_finish_scratch_floats(void) { return (long long)uad_grad_finish_scratch_floats(); }
+int uad_op_grad_finish(const uad_grad_finish_t* a, int fused, float* scratch, void* stream) {
+    if (!a || !scratch) return fail(UAD_ERR_INVALID, "grad_finish: null argument");
+    if ((a->slabs && (a->S < 1 || a->L < 1 || !a->dW)) || (a->colpart && (a->T < 1 || a->C < 1 || !a->gamma)) ||
+        (a->fin_partial && (a->fin_T < 1 || a->fin_C < 1 || !a->fin_gamma || !a->dwf || !a->dbf || !a->fin_red)))
+        return fail(UAD_ERR_INVALID, "grad_finish: a part with an input needs its sizes and outputs");
+    hipStream_t st = (hipStream_t)stream;
+    if (fused) {
+        if (!uad_grad_finish_takes(a->colpart ? a->C : 0, a->fin_partial ? a->fin_C : 0)) return fail(UAD_ERR_UNSUPPORTED, "grad_finish: C <= 512 and fin_C <= 64 in one launch");
+        UadGradFinish f;
+        memset(&f, 0, sizeof f);
+        f.partial = a->slabs; f.S = a->S; f.L = a->L; f.dW = a->dW;
+        f.colpart = a->colpart; f.T = a->T; f.C = a->C; f.gamma = a->gamma; f.rstd = a->rstd; f.dgamma = a->dgamma; f.dbeta = a->dbeta; f.dbias = a->dbias;
+        f.fin_partial = a->fin_partial; f.fin_T = a->fin_T; f.fin_C = a->fin_C; f.fin_gamma = a->fin_gamma;
+        f.dwf = a->dwf; f.dbf = a->dbf; f.fin_dgamma = a->fin_dgamma; f.fin_dbeta = a->fin_dbeta; f.fin_dbias = a->fin_dbias;
+        f.scratch = scratch;
+        uad_launch_grad_finish(f, st);
+    } else {      // the model's order on its side stream
+        if (a->fin_partial) {
+            uad_launch_reduce_partials(a->fin_partial, a->fin_T, 3 * a->fin_C + 1, 1.0f, a->fin_red, st);
+            uad_launch_final_gradfin(a->fin_red, a->fin_C, a->fin_gamma, a->rstd, a->dwf, a->dbf, a->fin_dgamma, a->fin_dbeta, a->fin_dbias, st);
+        }
+        if (a->slabs) uad_launch_reduce_partials(a->slabs, a->S, a->L, 1.0f, a->dW, st);
+        if (a->colpart) uad_launch_bn_grad_finalize(a->colpart, a->T, a->C, a->gamma, a->rstd, a->dgamma, a->dbeta, a->dbias, st, scratch);
+    }
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
 }  // extern "C"
