@@ -556,6 +556,37 @@ size_t uad_histogram_by_class_workspace(long long n);
 int uad_histogram_by_class(const float* in, const uint8_t* labels, long long n, int n_classes, const float* edges, int bins, const double* centre,
                            long long* counts, long long* class_count, double* sums, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sums in a defined order and the standardization map (csrc/uad_moments.hip) ---------------------------------
+ * NII.normalize(method='standardization') of utils/NII.py:53-75 (and its copy dataloaders/NRRD.py:39-60) on a resident volume: clamp to the
+ * percentiles, c = v - mean(v), out = c / std(c), where np.std subtracts the float32 mean of c again before it squares.  Three
+ * uad_shifted_sums calls and one uad_clamp_standardize call do it; the caller reads the 16 bytes of sums back between them and rounds
+ * each scalar to float32 once (utils/standardize.py states the whole in numpy, same bits):
+ *   (shift 0, centre 0) -> sum v          mean32 = f32(sum / n)
+ *   (mean32, 0)         -> sum c          m2_32  = f32(sum / n)
+ *   (mean32, m2_32)     -> sum e^2        var32  = f32(sum / n), std32 = sqrtf(var32)
+ * numpy adds in float32 in an order of its own; these sums are fp64 in the order below -- a stated deviation.
+ * uad_shifted_sums: for t_i = f32(f32(clamp(in[i])) - shift) and u_i = f32(t_i - centre), clamp(v) = (v < clamp_lo ? clamp_lo : v >
+ *   clamp_hi ? clamp_hi : v) as uad_clamp_scale (-inf / +inf = no bound), sums_out[0] = sum u_i and sums_out[1] = sum f32(u_i * u_i), both
+ *   fp64 on the device (8-byte aligned), in ONE pass over `in` (fp32 [n], device, 4-byte aligned) and with NO floating-point atomic.  Order:
+ *   tile T is in[T * UAD_SELECT_TILE ..); thread t of the tile adds the values T * UAD_SELECT_TILE + (r * 256 + t) * 4 + e, r = 0 .. 7, e =
+ *   0 .. 3, that lie below n -- 32 values, eight 16-byte chunks -- in that order to +0.0; the workgroup adds its 256 runs as a tree (level d
+ *   = 128, 64, ... 1: run t + d onto run t); one partial per tile goes to the workspace; one workgroup adds the partials t, t + 256, ... per
+ *   thread and its 256 runs with the same tree.  This is the order of uad_histogram_by_class's sums, except that the tiles are counted from
+ *   `in` and not from the 16-byte boundary below it: the order is a function of n alone, the result is bit-identical from run to run,
+ *   independent of the grid and of the alignment of `in`.  The longest chain of dependent additions is 32 + 8 + ceil(tiles / 256) + 8 <=
+ *   UAD_SHIFTED_SUMS_CHAIN for every accepted n, so a sum errs by at most UAD_SHIFTED_SUMS_CHAIN * 2^-53 * sum |terms| (to first order in
+ *   2^-53) against the exact sum of the same fp32 terms.  The terms themselves are fp32, unfused.
+ *   workspace: device memory of at least uad_shifted_sums_workspace(n) bytes (16 per tile), 16-byte aligned, owned by the caller, any
+ *   contents.  n == 0: UAD_OK, nothing launched, sums zeroed.  UAD_ERR_INVALID: a NULL pointer, a negative size, a misaligned pointer, a short
+ *   or misaligned workspace.  UAD_ERR_UNSUPPORTED: n > 2^31 - 1.
+ * uad_clamp_standardize: out[i] = f32(f32(clamp(in[i]) - mean) / std), a true fp32 division (std == 0 gives NaN / +-inf as numpy's does);
+ *   out may alias in.  UAD_ERR_INVALID: a NULL pointer with n > 0, a negative size, a pointer that is not 4-byte aligned. */
+enum { UAD_SHIFTED_SUMS_CHAIN = 1072 };
+size_t uad_shifted_sums_workspace(long long n);
+int uad_shifted_sums(const float* in, long long n, float clamp_lo, float clamp_hi, float shift, float centre, double* sums_out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int uad_clamp_standardize(const float* in, long long n, float clamp_lo, float clamp_hi, float mean, float std, float* out, void* stream);
+
 /* ---- f-AnoGAN (unified graph) ------------------------------------------------------------------------------
  * Replaces models/fanogan.py:11-84 (encoder + generator + critic graph) and the three optimisation phases of
  * trainers/fAnoGAN.py:45-77 (losses :50-66, the WGAN-GP penalty's tf.gradients :55-57, three Adams :71-77);

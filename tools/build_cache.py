@@ -23,6 +23,10 @@ engine (--device-resample or --device-stats) the whole path runs on the GPU (uad
 of the label slice centred on its centroid (not with --rotations), or --random-crops-per-slice N windows per slice whose corners come from a
 numpy RandomState seeded with --crop-seed S (one stream over all patients; the label map is cropped at the image's origins).  With a device
 engine the component measurements and the window gather run on the GPU (uad_cc_label, uad_cc_props, uad_crop2d) -- the same crops bit for bit.
+--normalization {scaling,standardization}: NII.normalize's method (utils/NII.py:53-75).  'scaling', the default, is what the reference's
+configurations use; 'standardization' is the default its loaders declare (MSLUB.py:49, BRAINWEB.py:55): the same percentile clamp, then
+(v - mean) / std over the whole volume (utils/standardize.py; with a device engine uad_shifted_sums and uad_clamp_standardize, same bits).
+The cached values are then not in [0, 1].
 """
 import argparse
 import json
@@ -57,6 +61,8 @@ def main():
     ap.add_argument('--crops', nargs=3, default=None, metavar=('MODE', 'W', 'H'), help="cache crops of W x H (width, height): MODE center | lesions | random")
     ap.add_argument('--random-crops-per-slice', type=int, default=5, metavar='N', help='--crops random: windows per slice and angle (numRandomCropsPerSlice)')
     ap.add_argument('--crop-seed', type=int, default=0, metavar='S', help='--crops random: seed of the numpy RandomState the corners are drawn from')
+    ap.add_argument('--normalization', choices=nifti.NORMALIZATIONS, default='scaling',
+                    help="NII.normalize's method: 'scaling' (clamp, divide by the maximum) or 'standardization' (clamp, subtract the mean, divide by the std)")
     a = ap.parse_args()
     if a.curvature_flow is not None and len(a.curvature_flow) not in (0, 2):
         ap.error('--curvature-flow takes no values or ITER STEP')
@@ -99,7 +105,7 @@ def main():
     info = nifti.build_cache(a.cache, patients, partition={'TRAIN': a.train, 'VAL': a.val, 'TEST': a.test}, seed=a.seed, engine=engine, axis=a.axis,
                              slice_start=a.start, slice_end=a.end, slice_resolution=(a.res, a.res), **({'rotations': tuple(a.rotations)} if list(a.rotations) != [0] else {}),
                              **({'device_stats': a.device_stats} if engine is not None and not loader else {}), **({'curvature_flow': flow} if flow is not None else {}),
-                             **loader, **crops)
+                             **loader, **crops, **({'normalization': a.normalization} if a.normalization != 'scaling' else {}))
     print(json.dumps(info))
 
 

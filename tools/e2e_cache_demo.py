@@ -1,5 +1,9 @@
 """End-to-end rehearsal of the real-data path on phantom volumes: NIfTI files -> tools/build_cache.py -> run.py --cache (HBM-resident
-training set, per-patient TEST volumes through Evaluation.evaluate)."""
+training set, per-patient TEST volumes through Evaluation.evaluate).
+
+    python tools/e2e_cache_demo.py [TRAINER MODEL] [--normalization {scaling,standardization}] [--device-stats]
+
+The two options go to tools/build_cache.py as they are (the cache of a standardized run holds values outside [0, 1])."""
 import os
 import subprocess
 import sys
@@ -33,9 +37,17 @@ def main():
         nifti.write_nifti(os.path.join(d, f'{name}_consensus_gt.nii.gz'), seg, dtype='u1')
         nifti.write_nifti(os.path.join(d, f'{name}_brainmask.nii.gz'), brain, dtype='u1')
     cache = os.path.join(tmp, 'cache')
+    argv, cache_options = sys.argv[1:], []
+    if '--normalization' in argv:
+        i = argv.index('--normalization')
+        cache_options += argv[i:i + 2]
+        del argv[i:i + 2]
+    if '--device-stats' in argv:
+        argv.remove('--device-stats')
+        cache_options.append('--device-stats')
     subprocess.check_call([sys.executable, os.path.join(ROOT, 'tools', 'build_cache.py'), os.path.join(tmp, 'data'), cache, '--res', '64', '--start', '2',
-                           '--end', '22', '--train', '0.5', '--val', '0.25', '--test', '0.25'])
-    trainer, model = (sys.argv[1], sys.argv[2]) if len(sys.argv) > 2 else ('AE', 'autoencoder')
+                           '--end', '22', '--train', '0.5', '--val', '0.25', '--test', '0.25'] + cache_options)
+    trainer, model = (argv[0], argv[1]) if len(argv) > 1 else ('AE', 'autoencoder')
     subprocess.check_call([sys.executable, os.path.join(ROOT, 'run.py'), '-t', trainer, '-m', model, '-E', '3', '-b', '8', '-w', '64', '-g', '64', '-z', '64',
                            '--cache', cache, '-c', os.path.join(tmp, 'none.json')], cwd=tmp)
 

@@ -59,6 +59,7 @@ AFFINE_MAX_K = 16                                                  # include/uad
 SELECT_ALL, SELECT_NONNEG = 0, 1
 SELECT_MAX_Q, SELECT_TILE, HISTOGRAM_MAX_BINS = 4, 8192, 1024      # include/uad_hip.h: UAD_SELECT_MAX_Q, UAD_SELECT_TILE, UAD_HISTOGRAM_MAX_BINS
 HISTOGRAM_MAX_CLASSES, HISTOGRAM_SUM_CHAIN = 4, 1073                # include/uad_hip.h: UAD_HISTOGRAM_MAX_CLASSES, UAD_HISTOGRAM_SUM_CHAIN
+SHIFTED_SUMS_CHAIN = 1072                                          # include/uad_hip.h: UAD_SHIFTED_SUMS_CHAIN
 GAN_ENCODER, GAN_GENERATOR, GAN_DISCRIMINATOR = 0, 1, 2
 GAN_UNIFIED, GAN_RESNET, GAN_ANOVAEGAN, GAN_AAE = 0, 1, 2, 3
 GAN_GROUP_VAE = 3
@@ -170,6 +171,9 @@ SYMBOLS = {
     'uad_histogram_by_class_workspace': (C.c_size_t, [C.c_longlong]),
     'uad_histogram_by_class': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    'uad_shifted_sums_workspace': (C.c_size_t, [C.c_longlong]),
+    'uad_shifted_sums': (C.c_int, [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'uad_clamp_standardize': (C.c_int, [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     'uad_rng_fill': (C.c_int, [C.POINTER(UadRngJob), C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_void_p]),
     'uad_clock_probe': (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_void_p]),
     'uad_gan_create': (C.c_int, [C.POINTER(UadGanConfig), C.POINTER(C.c_void_p)]),

@@ -559,6 +559,50 @@ class DeviceOps(OrderStatOps):
                                             float(scale), _ptr(out), self._stream()))
         return out
 
+    # ---------------------------------------------------------------- ordered sums and standardization (csrc/uad_moments.hip)
+    def shifted_sums_workspace(self, n):
+        """A workspace tensor for shifted_sums / standardize calls over up to n values (any contents)."""
+        nbytes = int(self.lib.uad_shifted_sums_workspace(int(n)))
+        return torch.empty(max(nbytes // 8, 2), device=self.device, dtype=torch.float64)
+
+    def shifted_sums(self, values, clamp_lo=None, clamp_hi=None, shift=0.0, centre=0.0, workspace=None):
+        """uad_shifted_sums: for u = f32(f32(clamp(v) - shift) - centre) -> (sum u, sum f32(u * u)) as Python floats: fp64 sums in the defined
+        order of include/uad_hip.h, bit-equal to utils.standardize.shifted_sums.  One pass, one 16-byte synchronising download."""
+        t = self._dev(values).reshape(-1)
+        ws = workspace if workspace is not None else self.shifted_sums_workspace(t.numel())
+        if not isinstance(ws, torch.Tensor) or ws.device != t.device or not ws.is_contiguous():
+            raise ValueError(f'workspace must be a contiguous tensor on {t.device} (shifted_sums_workspace gives one)')
+        sums = torch.empty(2, device=self.device, dtype=torch.float64)
+        _lib.check(self.lib.uad_shifted_sums(_ptr(t), t.numel(), -math.inf if clamp_lo is None else float(clamp_lo),
+                                             math.inf if clamp_hi is None else float(clamp_hi), float(shift), float(centre), _ptr(sums), _ptr(ws),
+                                             ws.numel() * ws.element_size(), self._stream()))
+        s = sums.cpu().numpy()
+        return float(s[0]), float(s[1])
+
+    last_moments = None                # (mean32, std32) of the latest standardize call on this object; None before the first
+
+    def standardize(self, values, clamp_lo=None, clamp_hi=None, out=None, return_moments=False):
+        """NII.normalize('standardization') of utils/NII.py:53-75 behind given clamp bounds (None = no bound), on the device: three shifted_sums
+        launches -- sum v, sum c, sum e^2, each read back and rounded to float32 once (utils.standardize.moments_from) -- and one
+        uad_clamp_standardize pass, out = (clamp(v) - mean32) / std32 -> fp32 device tensor of values' shape.  out: None, or a contiguous fp32
+        tensor on this device with values' number of elements (it may be `values` itself); anything else raises ValueError.
+        return_moments: -> (out, (mean32, std32)), the way to get the scalars of THIS call; they also stay in self.last_moments, which the
+        next call on this object overwrites, whatever stream or caller it comes from.  Bit-equal to utils.standardize.standardize_clamped."""
+        from .utils.standardize import moments_from
+        t = self._dev(values)
+        if out is None:
+            out = torch.empty_like(t)
+        elif (not isinstance(out, torch.Tensor) or out.device != t.device or out.dtype != torch.float32 or not out.is_contiguous()
+              or out.numel() != t.numel()):
+            raise ValueError(f'out must be a contiguous float32 tensor of {t.numel()} elements on {t.device}, got '
+                             f'{(out.dtype, tuple(out.shape), str(out.device), out.is_contiguous()) if isinstance(out, torch.Tensor) else type(out).__name__}')
+        ws = self.shifted_sums_workspace(t.numel())
+        mean32, std32 = moments_from(lambda shift, centre: self.shifted_sums(t, clamp_lo, clamp_hi, shift, centre, workspace=ws), t.numel())
+        self.last_moments = (mean32, std32)
+        _lib.check(self.lib.uad_clamp_standardize(_ptr(t), t.numel(), -math.inf if clamp_lo is None else float(clamp_lo),
+                                                  math.inf if clamp_hi is None else float(clamp_hi), float(mean32), float(std32), _ptr(out), self._stream()))
+        return (out, (mean32, std32)) if return_moments else out
+
     # ---------------------------------------------------------------- per-class histograms (csrc/uad_select.hip, csrc/uad_hist.hip)
     def _class_ids(self, ids, n):
         """-> contiguous uint8 device tensor [n] of class ids (a numpy array or a tensor of any integer type)."""

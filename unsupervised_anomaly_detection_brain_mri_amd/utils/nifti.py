@@ -20,6 +20,10 @@ device) for slices larger than `sliceResolution` and zero padding otherwise.
 `volume_to_slices(crops=...)` adds the reference's crop modes (`useCrops`: cropType 'center' | 'lesions' | 'random'; MSLUB.py:186-222,
 BRAINWEB.py:165-180): utils/crops.py states the component measurements and the window arithmetic, csrc/uad_crops.hip runs them on the device.
 
+`volume_to_slices(normalization='standardization')` takes NII.normalize's other method (NII.py:53-75; the default the reference's loaders
+declare, while its configurations use 'scaling') in the place of the scaling: utils/standardize.py states it -- three fp64 sums in a defined
+order, each scalar rounded to float32 once --, csrc/uad_moments.hip runs it on the device with the same bits.
+
 `build_cache` turns a list of patients into the slice cache of utils/slice_cache.py with the reference's patient-level TRAIN / VAL / TEST
 partition (a permutation of the patients cut at floor(fraction * n), MSLUB.py:71-90)."""
 import gzip
@@ -138,11 +142,15 @@ def _has_order_stats(engine):
     return engine is not None and all(hasattr(engine, op) for op in ('select_quantiles', 'clamp_scale', 'percentile'))
 
 
-def _normalize_scaling_on(engine, v, lower, upper):
-    """normalize_scaling of an fp32 array resident with `engine` (engine._dev), without a sort and without leaving the engine: ONE select call
-    brackets the lower percentile, the upper percentile and the maximum (q = {lower, upper, 1}).  Clamping is monotone, so the order
-    statistics of the lower-clamped array are the clamped order statistics: the upper percentile is interpolated from the clamped brackets,
-    exactly what np.percentile returns after `v[v < q] = q`.  Then one clamp-and-scale pass.  NaN-free input."""
+def _has_standardize(engine):
+    return _has_order_stats(engine) and all(hasattr(engine, op) for op in ('shifted_sums', 'standardize'))
+
+
+def _clamp_bounds_on(engine, v, lower, upper):
+    """The percentile clamp of NII.normalize on an fp32 array resident with `engine`, without a sort: ONE select call brackets the lower
+    percentile, the upper percentile and the maximum (q = {lower, upper, 1}).  Clamping is monotone, so the order statistics of the
+    lower-clamped array are the clamped order statistics: the upper percentile is interpolated from the clamped brackets, exactly what
+    np.percentile returns after `v[v < q] = q`.  -> (clamp_lo, clamp_hi, top): float32 bounds (None = no clamp) and the clamped maximum."""
     from .order_stats import finish_linear, percentile_fractions
     f32 = np.dtype(np.float32)
     ql = percentile_fractions(0 if lower is None else lower, f32)
@@ -157,8 +165,31 @@ def _normalize_scaling_on(engine, v, lower, upper):
     if upper is not None:
         clamp_hi = finish_linear(m, lo[:, 1], hi[:, 1], qu, f32)[0]
         top = clamp_hi if top > clamp_hi else top
+    return clamp_lo, clamp_hi, top
+
+
+def _normalize_scaling_on(engine, v, lower, upper):
+    """normalize_scaling of an fp32 array resident with `engine` (engine._dev), without leaving the engine: the one select call of
+    _clamp_bounds_on, then one clamp-and-scale pass.  NaN-free input."""
+    clamp_lo, clamp_hi, top = _clamp_bounds_on(engine, v, lower, upper)
     scale = np.float32(1.0 / top) if top > 0.0 else np.float32(1.0)
     return engine.clamp_scale(v, clamp_lo, clamp_hi, scale)
+
+
+def _normalize_standardization_on(engine, v, lower, upper):
+    """normalize_standardization of an fp32 array resident with `engine`: the one select call of _clamp_bounds_on, then engine.standardize --
+    three ordered-sum launches with a 16-byte download each and one clamp-and-standardize pass.  NaN-free input."""
+    clamp_lo, clamp_hi, _ = _clamp_bounds_on(engine, v, lower, upper)
+    return engine.standardize(v, clamp_lo, clamp_hi)
+
+
+NORMALIZATIONS = ('scaling', 'standardization')         # NII.normalize's methods (NII.py:53-75)
+
+
+def _normalization_setting(normalization):
+    if normalization not in NORMALIZATIONS:
+        raise ValueError(f"normalization must be 'scaling' or 'standardization', got {normalization!r}")
+    return normalization
 
 
 def normalize_scaling(vol, lower=0, upper=99.8, engine=None):
@@ -181,6 +212,21 @@ def normalize_scaling(vol, lower=0, upper=99.8, engine=None):
     return v
 
 
+def normalize_standardization(vol, lower=0, upper=99.8, engine=None):
+    """NII.normalize(method='standardization', lowerpercentile, upperpercentile) (NII.py:53-75): the percentile clamp of normalize_scaling, then
+    c = v - mean(v) and c / std(c) in float32.  utils/standardize.py states it; its three sums are fp64 sums in a defined order, each scalar
+    rounded to float32 once -- not numpy's float32 sums in numpy's own order (a stated deviation; DESIGN).  A constant volume gives NaN.
+    engine: an engine with the order statistics and the ordered sums (device_ops.DeviceOps.select_quantiles / shifted_sums / standardize): one
+    select call gives the clamp bounds, three sum launches and one map pass follow; the same float32 array comes back, bit for bit (but
+    for the sign of a zero-valued lower clamp, as in normalize_scaling, which shows only where the mean is zero too).  Python-scalar
+    percentiles and NaN-free input; an engine without the ops gets the host statement."""
+    if _has_standardize(engine) and all(p is None or isinstance(p, (int, float)) for p in (lower, upper)):
+        out = _normalize_standardization_on(engine, engine._dev(np.ascontiguousarray(vol, np.float32)), lower, upper)
+        return out.cpu().numpy().reshape(np.shape(vol))
+    from .standardize import standardize
+    return standardize(vol, lower, upper)
+
+
 def crop_center(img, cropx, cropy):
     """utils/image_utils.py:4-12."""
     y, x = img.shape[:2]
@@ -191,7 +237,7 @@ def crop_center(img, cropx, cropy):
 def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0, slice_end=155, slice_resolution=None, skull_stripping=True,
                      view_mapping=None, empty_percentile=90, empty_thresh=0.2, denoise=False, rotations=(0,), center_crop=None, engine=None,
                      device_stats=None, device_rotate=None, curvature_flow=None, spacing=(1, 1, 1), loader='mslub', skull_removal=True,
-                     background_removal=True, crops=None, rng=None):
+                     background_removal=True, crops=None, rng=None, normalization='scaling'):
     """-> (images [k,H,W] float32 in [0,1], labels [k,H,W] float32 in {0,1}, slice indices kept).
     rotations: angles in degrees, one output per angle and slice (dataloaders/BRAINWEB.py:156-162: scipy.ndimage.rotate, reshape False, the label
     map with mode 'nearest'); center_crop (width, height): the `useCrops` / cropType 'center' option (MSLUB.py:206-210).
@@ -232,14 +278,23 @@ def volume_to_slices(vol, seg=None, brainmask=None, axis='axial', slice_start=0,
     pixel; random crops in draw order); `kept` carries the slice index of every crop.
     With an engine that has `region_props` and `crop` (device_ops.DeviceOps) the prepared image batch and label batch stay on the device, the
     labels go through region_props(slab=1), the origins are formed on the host from the small table, one crop call serves the images and
-    one the labels, and one download follows.  Without such an engine: the host statement.  The same crops bit for bit."""
+    one the labels, and one download follows.  Without such an engine: the host statement.  The same crops bit for bit.
+    normalization: 'scaling' (default; what the reference's configurations use) | 'standardization' (the default its loaders declare,
+    MSLUB.py:49, BRAINWEB.py:55): NII.normalize's method (NII.py:53-75), with the same [0, 99.8] percentile clamp, for both loaders --
+    normalize_standardization in the place of normalize_scaling; the values are then no longer in [0, 1].  Everything behind it is applied
+    unchanged, as the reference applies it whatever the method: the empty-slice filter's `percentile < 0.2`, BrainWeb's constant-slice filter,
+    zoom / resize, rotations, crops.  With device_stats (or loader='brainweb' on an engine with `resize`) and an engine that has the ordered
+    sums (device_ops.DeviceOps.shifted_sums / standardize) the volume stays resident: no extra upload or download, the same kept slices
+    and the same bits as the host route; an engine without them takes the host statement for the normalisation (both loaders; only an
+    explicit device_stats=True with such an engine raises).  Any other value raises ValueError."""
+    _normalization_setting(normalization)
     spec = _crop_setting(crops, center_crop, rotations)
     if spec is not None and spec[0] == 'center':
         center_crop, spec = (spec[1], spec[2]), None
     on_device = spec is not None and hasattr(engine, 'region_props') and hasattr(engine, 'crop')
     out = _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_resolution, skull_stripping, view_mapping, empty_percentile, empty_thresh,
                            denoise, rotations, center_crop, engine, device_stats, device_rotate, curvature_flow, spacing, loader, skull_removal, background_removal,
-                           resident=on_device)
+                           resident=on_device, normalization=normalization)
     if spec is None:
         return out
     return _crop_slices(out[0], out[1], out[2], spec, rng, engine if on_device else None)
@@ -307,7 +362,7 @@ def _resident_result(sds, sss, kept_s, rotations):
 
 
 def _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_resolution, skull_stripping, view_mapping, empty_percentile, empty_thresh, denoise,
-                     rotations, center_crop, engine, device_stats, device_rotate, curvature_flow, spacing, loader, skull_removal, background_removal, resident=False):
+                     rotations, center_crop, engine, device_stats, device_rotate, curvature_flow, spacing, loader, skull_removal, background_removal, resident=False, normalization='scaling'):
     """volume_to_slices up to and including rotations and center_crop.  resident: leave batches that are on the device there (device tensors
     [k,H,W] come back in the place of host arrays) when no host step is left to do, i.e. unless a non-zero angle has to be rotated on the host."""
     from scipy.ndimage import rotate, zoom
@@ -317,7 +372,7 @@ def _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_re
         if _flow_setting(curvature_flow) is not None or denoise:
             raise ValueError("loader='brainweb' does not denoise: the reference calls nii.denoise() for the MS datasets only")
         return _brainweb_to_slices(vol, seg, axis, slice_start, slice_end, slice_resolution, view_mapping, rotations, center_crop, engine, device_rotate,
-                                   skull_removal, background_removal, resident)
+                                   skull_removal, background_removal, resident, normalization)
     if loader != 'mslub':
         raise ValueError(f"loader must be 'mslub' or 'brainweb', got {loader!r}")
     if denoise:
@@ -330,10 +385,13 @@ def _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_re
     if seg is None:
         seg = np.zeros_like(vol)
     seg = (np.asarray(seg) >= 0.9).astype(np.float64)                       # MSLUB.py:264-265
+    standardization = _normalization_setting(normalization) == 'standardization'
     if device_stats is None:
-        device_stats = _has_order_stats(engine)
+        device_stats = _has_standardize(engine) if standardization else _has_order_stats(engine)
     elif device_stats and not _has_order_stats(engine):
         raise ValueError('device_stats needs an engine with the order-statistic ops (select_quantiles, clamp_scale)')
+    elif device_stats and standardization and not _has_standardize(engine):
+        raise ValueError("device_stats with normalization='standardization' needs an engine with the ordered sums (shifted_sums, standardize)")
     flow_dev = None
     if flow is not None:                                                    # nii.denoise(), before the skull map (MSLUB.py:242,257)
         if hasattr(engine, 'curvature_flow'):
@@ -362,7 +420,7 @@ def _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_re
             moved = flow_dev.movedim(ax, 0).to(torch.float32).contiguous()
         else:
             moved = engine._dev(np.ascontiguousarray(np.moveaxis(vol, ax, 0), np.float32))
-        vol_dev = _normalize_scaling_on(engine, moved, 0, 99.8)
+        vol_dev = _normalize_standardization_on(engine, moved, 0, 99.8) if standardization else _normalize_scaling_on(engine, moved, 0, 99.8)
         s_end = min(slice_end, vol.shape[ax])
         if s_end > slice_start:
             stat = engine.percentile(vol_dev[slice_start:s_end], empty_percentile, segments=s_end - slice_start)
@@ -370,7 +428,7 @@ def _prepared_slices(vol, seg, brainmask, axis, slice_start, slice_end, slice_re
         else:
             keep_dev = []
     else:
-        vol = normalize_scaling(vol)
+        vol = normalize_standardization(vol) if standardization else normalize_scaling(vol)
     sds, sss, kept_s = [], [], []
     for s in (keep_dev if device_stats else range(slice_start, min(slice_end, vol.shape[ax]))):
         idx = [slice(None)] * 3
@@ -435,10 +493,10 @@ BRAINWEB_BACKGROUND, BRAINWEB_LESION = 0, 10
 
 
 def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolution, view_mapping, rotations, center_crop, engine, device_rotate,
-                        skull_removal, background_removal, resident=False):
+                        skull_removal, background_removal, resident=False, normalization='scaling'):
     """volume_to_slices(loader='brainweb'): dataloaders/BRAINWEB.py:125-185 with load_volume_and_groundtruth (:266-292) on the repo's arrays.
     NaN -> 0; the skull map is 1 except at the dropped tissue classes and multiplies the volume when either flag is set; the lesion map is
-    tissue == 10; normalize_scaling(0, 99.8); then per slice of [slice_start, min(slice_end, n)): a CONSTANT slice (numpy.unique(...).size == 1,
+    tissue == 10; normalize_scaling(0, 99.8) -- or, with normalization='standardization', normalize_standardization(0, 99.8) --; then per slice of [slice_start, min(slice_end, n)): a CONSTANT slice (numpy.unique(...).size == 1,
     :133) is skipped; a slice larger than slice_resolution on either axis is resized -- utils/resize.py's resize_linear for the image,
     resize_nearest for the label -- and every other slice is zero-padded, centred with `//` starts (:144-154).
     The output-shape quirk: the reference hands tuple(sliceResolution) to cv2.resize, which reads it as (width, height), so a RESIZED slice
@@ -465,7 +523,9 @@ def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolut
         raise ValueError('the tissue-class volume must hold integer class values 0 .. 255')
     dropped = (BRAINWEB_SKULL_CLASSES if skull_removal else ()) + ((BRAINWEB_BACKGROUND,) if background_removal else ())
     keep = [c for c in range(256) if c not in dropped]
-    on_device = engine is not None and hasattr(engine, 'resize')
+    standardization = _normalization_setting(normalization) == 'standardization'
+    # an engine with `resize` but without the ordered sums: the host route below, as the MS loaders' path does without device_stats
+    on_device = engine is not None and hasattr(engine, 'resize') and (not standardization or _has_standardize(engine))
     if device_rotate is None:
         device_rotate = hasattr(engine, 'rotate')
     elif device_rotate and not hasattr(engine, 'rotate'):
@@ -480,7 +540,7 @@ def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolut
         import torch
         moved = engine._dev(np.ascontiguousarray(np.moveaxis(vol, ax, 0), np.float32))
         masked, lesion = engine.mask_by_label(moved, np.ascontiguousarray(np.moveaxis(tissue, ax, 0)), keep, BRAINWEB_LESION, out=moved)
-        vol_dev = _normalize_scaling_on(engine, masked, 0, 99.8)
+        vol_dev = _normalize_standardization_on(engine, masked, 0, 99.8) if standardization else _normalize_scaling_on(engine, masked, 0, 99.8)
         kept_s = []
         if s_end > slice_start:
             _, lo, hi = engine.select_quantiles(vol_dev[slice_start:s_end], [0.0, 1.0], [False, False], segments=s_end - slice_start)
@@ -510,7 +570,7 @@ def _brainweb_to_slices(vol, tissue, axis, slice_start, slice_end, slice_resolut
         if dropped:
             vol = np.where(np.isin(tissue, dropped), 0.0, vol)              # :272-289
         lesion = (tissue == BRAINWEB_LESION).astype(np.float32)             # :283-286
-        vol = normalize_scaling(vol)                                        # :292
+        vol = normalize_standardization(vol) if standardization else normalize_scaling(vol)      # :292
         sds, sss, kept_s = [], [], []
         for s in range(slice_start, s_end):
             idx = [slice(None)] * 3
@@ -606,11 +666,15 @@ def partition_patients(n_patients, partition=None, rng=None):
 
 def build_cache(directory, patients, partition=None, seed=0, engine=None, **slice_options):
     """patients: [{'name', 'volume': path, 'groundtruth': path or None, 'skullmap': path or None}] -> slice cache in `directory`.
-    slice_options: volume_to_slices keywords (device_stats, curvature_flow, loader / skull_removal / background_removal, crops / rng among them: one
+    slice_options: volume_to_slices keywords (device_stats, curvature_flow, normalization, loader / skull_removal / background_removal, crops / rng among them: one
     `rng` serves all patients in order, and it is not recorded in the cache's options; with
     loader='brainweb' 'groundtruth' names the tissue-class volume and 'skullmap' is ignored); engine: volume_to_slices' device resampler / order
     statistics / curvature flow.  Unless slice_options names a `spacing`, each volume gets its own from its header: abs(pixdim[1:4]), a zero
     replaced by 1.0.
+    The label map's "brain" class is `image > 0`, which is the skull-stripped brain only with normalization='scaling': a standardized
+    background is negative and zero is the volume's mean, so with 'standardization' that class marks the pixels above the mean (and the
+    lesion class stays exact).  Whatever reads the cache's brain mask (next_batch(return_brainmask=True), the context-encoder boxes, the
+    evaluation's mask) needs a 'scaling' cache; a standardized cache serves training on the images.
     Returns the index dict that was written."""
     from .slice_cache import SET_TYPES, write_cache
     split = partition_patients(len(patients), partition, np.random.default_rng(seed))
