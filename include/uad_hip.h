@@ -556,6 +556,28 @@ size_t uad_histogram_by_class_workspace(long long n);
 int uad_histogram_by_class(const float* in, const uint8_t* labels, long long n, int n_classes, const float* edges, int bins, const double* centre,
                            long long* counts, long long* class_count, double* sums, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-segment voxel confusion counts (csrc/uad_confusion.hip) -------------------------------------------------
+ * Metrics.confusion_matrix / dice / precision / recall / tpr / vd of trainers/Metrics.py as utils/Evaluation.py:452-500 calls them, per
+ * patient and over the whole test set: each of those scalars is a function of four integers per patient (utils/confusion.py states both
+ * halves in numpy).
+ * uad_confusion_by_segment: for each of n_segments contiguous segments of a flat voxel array, counts[s] = {TP, FP, FN, TN} (int64
+ *   [n_segments, 4], device, 8-byte aligned) of pred[i] > thr against gt[i] != 0 over i in [seg_offsets[s], seg_offsets[s + 1]).
+ *   pred: fp32 [n], device, 4-byte aligned (the output of uad_cc_filter, or raw residuals).  thr: the comparison is an ordered `>`, so a NaN
+ *   is not a prediction, as in numpy.  gt: u8 [n], device, any byte alignment, non-zero = lesion.  seg_offsets: int64 [n_segments + 1], device,
+ *   8-byte aligned, non-decreasing, 0 <= seg_offsets[0] and seg_offsets[n_segments] <= n (the kernels cut an entry outside [0, n] to that
+ *   range); empty segments are legal, voxels outside every segment are not counted.  max_seg_len: at least every segment's length; it sizes
+ *   the grid only.  counts is zeroed in-stream by the call; TN is formed as length - TP - FP - FN.  Asynchronous, no workspace.
+ *   Grid = (a quarter of the tiles of UAD_SELECT_TILE values of the longest segment, segments), held to 2048 workgroups but one per segment at least, which stride over
+ *   a segment's tiles.
+ *   16-byte loads of the values and dword loads of the labels counted from the 16-byte boundary below the segment's first value, guarded
+ *   value-by-value head and tail; three 32-bit counters per thread (a thread sees fewer than 2^23 voxels), one tree reduction in LDS and
+ *   three 64-bit integer atomics per workgroup.  Integer atomics only: the counts depend on neither the order of arrival nor the grid.
+ *   Reads 4 + 1 B per voxel of a segment, once.
+ *   n_segments == 0 or n == 0: UAD_OK, counts zeroed, nothing launched.  UAD_ERR_INVALID: a NULL pointer that is needed, a negative size,
+ *   n_segments > 65535, a misaligned pred / seg_offsets / counts.  UAD_ERR_UNSUPPORTED: n > 2^31 - 1. */
+int uad_confusion_by_segment(const float* pred, float thr, const uint8_t* gt, long long n, const long long* seg_offsets, int n_segments,
+                             long long max_seg_len, long long* counts, void* stream);
+
 /* ---- sums in a defined order and the standardization map (csrc/uad_moments.hip) ---------------------------------
  * NII.normalize(method='standardization') of utils/NII.py:53-75 (and its copy dataloaders/NRRD.py:39-60) on a resident volume: clamp to the
  * percentiles, c = v - mean(v), out = c / std(c), where np.std subtracts the float32 mean of c again before it squares.  Three

@@ -171,6 +171,7 @@ SYMBOLS = {
     'uad_histogram_by_class_workspace': (C.c_size_t, [C.c_longlong]),
     'uad_histogram_by_class': (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    'uad_confusion_by_segment': (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     'uad_shifted_sums_workspace': (C.c_size_t, [C.c_longlong]),
     'uad_shifted_sums': (C.c_int, [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'uad_clamp_standardize': (C.c_int, [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),

@@ -1,5 +1,5 @@
 """The model-independent device ops of the evaluation and ingestion paths (erosion, 3-D median, splines, curvature flow, resize, component
-labelling, crops, 8-bit rendering, order statistics, histograms, residual maps, sort-based metrics) as a class that stands alone: the C
+labelling, crops, 8-bit rendering, order statistics, histograms, confusion counts, residual maps, sort-based metrics) as a class that stands alone: the C
 entry points take no model handle, so neither does DeviceOps.  The AE-family Engine and the f-AnoGAN GanEngine inherit it."""
 import ctypes as C
 import math
@@ -294,6 +294,47 @@ class DeviceOps(OrderStatOps):
                                                self._stream()))
         tps, fps, fns = (int(c) for c in counts.cpu().tolist())
         return tps, fps, fns
+
+    def _label_bytes(self, gt, n):
+        """-> contiguous uint8 device tensor [n], non-zero = lesion: uint8 data as it is (a resident tensor is not copied, a host array goes up
+        once); a numpy array or a tensor of any other integer / bool dtype is made uint8 (`!= 0`) where it lives and uploaded once."""
+        if isinstance(gt, torch.Tensor):
+            if gt.dtype.is_floating_point or gt.dtype.is_complex:
+                raise ValueError(f'labels must be of an integer or bool dtype, got {gt.dtype}')
+            t = gt.reshape(-1)
+            if t.dtype != torch.uint8:
+                t = (t != 0).to(torch.uint8)
+            t = t.to(self.device).contiguous()
+        else:
+            a = np.asarray(gt)
+            if not (np.issubdtype(a.dtype, np.integer) or a.dtype == bool):
+                raise ValueError(f'labels must be of an integer or bool dtype, got {a.dtype}')
+            a = a.reshape(-1)
+            t = torch.from_numpy(np.ascontiguousarray(a if a.dtype == np.uint8 else (a != 0).view(np.uint8))).to(self.device)
+        if t.numel() != n:
+            raise ValueError(f'{t.numel()} labels for {n} values')
+        return t
+
+    def confusion_counts(self, pred, gt, lengths, thr=0.0):
+        """utils.confusion.confusion_counts on the device (uad_confusion_by_segment): {TP, FP, FN, TN} of `pred > thr` against `gt != 0` for each
+        of the contiguous segments of `lengths` voxels (the patients of a stacked volume) -> numpy int64 [P, 4].  pred: a device fp32 tensor of
+        any shape, or an array that is uploaded; gt: see _label_bytes; lengths: non-negative integers that add up to the number of voxels
+        (ValueError otherwise); thr is taken as float32.  Three launches (zero, count, TN), of which the count reads 5 B per voxel, one download of 32 B per segment."""
+        from .utils.confusion import segment_offsets
+        t = self._dev(pred).reshape(-1)
+        n = t.numel()
+        lab = self._label_bytes(gt, n)
+        offsets = segment_offsets(lengths, n)
+        n_seg = offsets.size - 1
+        if n_seg > 65535:
+            raise ValueError(f'at most 65535 segments a call, got {n_seg}')
+        if n_seg == 0:
+            return np.zeros((0, 4), np.int64)
+        off = torch.from_numpy(offsets).to(self.device)
+        counts = torch.empty((n_seg, 4), device=self.device, dtype=torch.int64)
+        _lib.check(self.lib.uad_confusion_by_segment(_ptr(t), float(thr), _ptr(lab), n, _ptr(off), n_seg, int(np.diff(offsets).max()), _ptr(counts),
+                                                     self._stream()))
+        return counts.cpu().numpy()
 
     def region_props(self, volume_or_labels, slab=0):
         """skimage's label + regionprops as dataloaders/MSLUB.py:201-206 use them, on the device (uad_cc_label + uad_cc_props; the statement is

@@ -25,6 +25,7 @@ import scipy.ndimage
 import torch
 
 from ..trainers import Metrics
+from .confusion import metrics_from_counts
 
 
 def should(dictionary, key):
@@ -247,10 +248,11 @@ def _threshold_at_precision(sc, d_all, l_all, precision):
     return float(th[np.argmax(prec <= precision)])
 
 
-def _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, options):
+def _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, options, counts=None):
     """utils/Evaluation.py:439-500: the lesion-wise half of the result dictionary.  The volume thresholded at 70 % precision is filtered
     and compared with every patient's label volume on the device (uad_cc_filter, uad_detection_rate); only three counters per patient
-    come back."""
+    come back.  counts: None, or the per-patient {TP, FP, FN, TN} of the final prediction (engine.confusion_counts): TP / FP / TN / FN / TPR /
+    FPR / VD come from their column sums and `pred`, the host copy of the prediction, is not looked at (it may be None)."""
     eng = model.engine
     if options.get('threshold', 'bestdice') == 'bestdice':
         pred70 = eng.cc_filter((stacked > float(thr70)).to(torch.float32), 7)
@@ -270,11 +272,18 @@ def _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, opti
             per_patient = np.array(ev[key + 'PerPatient'], np.float64)
             ev[key + 'PerPatientMean'] = float(np.mean(per_patient))
             ev[key + 'PerPatientStd'] = float(np.std(per_patient))
-        gt_all = np.concatenate(gts, axis=0)
-        ev['TP'], ev['FP'], ev['TN'], ev['FN'] = (int(c) for c in Metrics.confusion_matrix(pred, gt_all))
-        ev['TPR'] = float(Metrics.tpr(pred, gt_all))
-        ev['FPR'] = float(Metrics.tpr(pred, gt_all))       # (the reference computes FPR with Metrics.tpr, :490, sic)
-        ev['VD'] = float(Metrics.vd(pred, gt_all))
+        if counts is not None:
+            overall = metrics_from_counts(counts.sum(axis=0))
+            ev['TP'], ev['FP'], ev['TN'], ev['FN'] = (int(c) for c in overall['confusion'])
+            ev['TPR'] = float(overall['tpr'])
+            ev['FPR'] = float(overall['tpr'])                  # (the reference computes FPR with Metrics.tpr, :490, sic)
+            ev['VD'] = float(overall['vd'])
+        else:
+            gt_all = np.concatenate(gts, axis=0)
+            ev['TP'], ev['FP'], ev['TN'], ev['FN'] = (int(c) for c in Metrics.confusion_matrix(pred, gt_all))
+            ev['TPR'] = float(Metrics.tpr(pred, gt_all))
+            ev['FPR'] = float(Metrics.tpr(pred, gt_all))       # (the reference computes FPR with Metrics.tpr, :490, sic)
+            ev['VD'] = float(Metrics.vd(pred, gt_all))
     ev['TPRCC'] = ev['TPCC'] / (ev['TPCC'] + ev['FNCC']) if ev['TPCC'] + ev['FNCC'] > 0 else 0.0
     ev['PrecisionCC'] = ev['TPCC'] / (ev['TPCC'] + ev['FPCC']) if ev['TPCC'] + ev['FPCC'] > 0 else 0.0
 
@@ -282,7 +291,9 @@ def _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, opti
 def _score_diffs(model, diffs, labels, options, variances=None, keep=None):
     """The metric tail of utils/Evaluation.py:416-500 on per-patient residual volumes (device tensors [S,H,W]) and label maps: the
     voxel-wise scalars and, from _lesionwise_keys, TPCC / FPCC / FNCC / TPRCC / PrecisionCC, TP / FP / TN / FN / TPR / FPR / VD and the
-    per-patient means / standard deviations.  keep: None, or a dict that receives 'pred_dev', the final filtered prediction [P*S,H,W] on the
+    per-patient means / standard deviations.  With an engine that has confusion_counts the voxel-wise scalars come from four integers per
+    patient counted on the resident prediction (utils/confusion.py) and the prediction is not downloaded; without it, from trainers/Metrics.py
+    on the downloaded volume -- the same dictionary either way.  keep: None, or a dict that receives 'pred_dev', the final filtered prediction [P*S,H,W] on the
     device (the overlay images of evaluate()), and with Monte-Carlo variances 'variance_p998', their 99.8th percentile (the range of the
     variance histograms of evaluate())."""
     d_all = torch.cat([d.reshape(-1) for d in diffs])
@@ -301,20 +312,35 @@ def _score_diffs(model, diffs, labels, options, variances=None, keep=None):
     pred_dev = model.engine.cc_filter((stacked > float(thr)).to(torch.float32), 7)
     if keep is not None:
         keep['pred_dev'] = pred_dev
-    pred = pred_dev.cpu().numpy() > 0
     gts = [np.asarray(l).reshape(d.shape).astype(bool) for d, l in zip(diffs, labels)]
-    ev['DiceScore'] = Metrics.dice(pred, np.concatenate(gts, axis=0))
-    ev['DiceScorePerPatient'], ev['PrecisionPerPatient'], ev['RecallPerPatient'] = [], [], []
-    s0 = 0
-    with np.errstate(divide='ignore', invalid='ignore'):
-        for d, g in zip(diffs, gts):
-            sub = pred[s0:s0 + d.shape[0]]
-            s0 += d.shape[0]
-            ev['DiceScorePerPatient'].append(Metrics.dice(sub, g))
-            ev['PrecisionPerPatient'].append(Metrics.precision(sub, g))
-            ev['RecallPerPatient'].append(Metrics.recall(sub, g))
+    confusion = getattr(model.engine, 'confusion_counts', None)
+    if confusion is not None:
+        # four integers per patient (uad_confusion_by_segment on the resident prediction; the label maps go up once, as bytes): every scalar
+        # below is Metrics' own expression on them (utils/confusion.py), and the prediction volume stays on the device
+        pred = None
+        counts = confusion(pred_dev, np.concatenate([g.reshape(-1) for g in gts]).view(np.uint8), [int(d.numel()) for d in diffs], 0.0)
+        ev['DiceScore'] = metrics_from_counts(counts.sum(axis=0))['dice']
+        ev['DiceScorePerPatient'], ev['PrecisionPerPatient'], ev['RecallPerPatient'] = [], [], []
+        for row in counts:
+            m = metrics_from_counts(row)
+            ev['DiceScorePerPatient'].append(m['dice'])
+            ev['PrecisionPerPatient'].append(m['precision'])
+            ev['RecallPerPatient'].append(m['recall'])
+    else:                                            # host stand-in engine: the host statements on the downloaded prediction
+        counts = None
+        pred = pred_dev.cpu().numpy() > 0
+        ev['DiceScore'] = Metrics.dice(pred, np.concatenate(gts, axis=0))
+        ev['DiceScorePerPatient'], ev['PrecisionPerPatient'], ev['RecallPerPatient'] = [], [], []
+        s0 = 0
+        with np.errstate(divide='ignore', invalid='ignore'):
+            for d, g in zip(diffs, gts):
+                sub = pred[s0:s0 + d.shape[0]]
+                s0 += d.shape[0]
+                ev['DiceScorePerPatient'].append(Metrics.dice(sub, g))
+                ev['PrecisionPerPatient'].append(Metrics.precision(sub, g))
+                ev['RecallPerPatient'].append(Metrics.recall(sub, g))
     ev['Dice'] = ev['DiceScorePerPatient']
-    _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, options)
+    _lesionwise_keys(ev, model, stacked, pred_dev, pred, thr70, diffs, gts, options, counts)
     if variances:
         # utils/Evaluation.py:404-408: histogram of the epistemic variances (50 bins, 1e-5 .. their 99.8th percentile)
         ev['epistemic_variance'] = np.concatenate(variances, axis=0)
