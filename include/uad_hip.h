@@ -799,6 +799,67 @@ typedef struct {
 long long uad_op_grad_finish_scratch_floats(void);
 int uad_op_grad_finish(const uad_grad_finish_t* a, int fused, float* scratch, void* stream);
 
+/* ---- the step's small kernels, ONE launch each on caller-supplied tensors (csrc/uad_misc.hip; uad_op_tv_dxhat: csrc/uad_gmvae.hip) ----
+ * Each entry runs the launcher the engines run, asynchronously on `stream`, and allocates nothing.  Outside the kernel's domain (stated per entry) it
+ * launches nothing and returns UAD_ERR_INVALID (a NULL pointer that is needed, a size below 1, a misaligned vector operand) or UAD_ERR_UNSUPPORTED (a
+ * width or count no kernel form takes).
+ *
+ * uad_op_final: last 1x1 conv (C -> 1) + L1 loss on c_last [N,H,W,C] (pre-BN output of the last decoder block): a = lrelu_alpha(scale * mult * c + shift),
+ *   x_hat = a . wf + bf[0], l1_map = |x_hat - x| (optional), rec_partial[N][B] = per-block sums of |x_hat - x|, B = uad_op_final_blocks(H, W).
+ *   d_c == NULL: forward only.  Otherwise s = dxhat_in ? dxhat_in[pixel] : sign(x_hat - x) * inv_batch (sign(0) = 0), d_c = s wf lrelu'(bn) scale mult, and
+ *   red_partial[N * B][3 C + 1] = per-block sums of {d wf = s a, S1 = d bn, S2 = d bn * c, d bf = s}.  Domain: C in {4, 8, 16, 32, 64} (C / 4 lanes of a
+ *   wave share a pixel; 3 C + 2 partials fit the kernel's 200 LDS floats), N <= 65535, c_last / d_c / scale / shift / wf 16-byte aligned. */
+typedef struct {
+    int N, H, W, C;
+    const float *c_last, *scale, *shift; float alpha, mult;
+    const float *wf, *bf, *x;
+    float *x_hat, *l1_map, *rec_partial;
+    float *d_c, *red_partial; float inv_batch; const float* dxhat_in;
+} uad_final_t;
+int uad_op_final_blocks(int H, int W);
+int uad_op_final(const uad_final_t* a, void* stream);
+/* Reparameterisation and KL, one wave per sample, [n, zdim] tensors.  Samples [0, n_vae): m = mu_raw * mask_mu, l = ls_raw * mask_ls, sigma = exp(l),
+ *   z = m + eps * sigma, kl[i] = 0.5 sum (m^2 + sigma^2 - 2 l - 1).  Samples [n_vae, n) (ceVAE context branch): m = mu_raw * mask_mu_ce[i - n_vae], z = m,
+ *   ls = 0, sigma = 1, kl = 0.  Backward: dmu_raw = (dz + mu * inv_batch) * mask_mu, dls_raw = (dz * eps * sigma + (sigma^2 - 1) * inv_batch) * mask_ls;
+ *   context samples: dmu_raw = dz * mask_mu_ce, dls_raw = 0.  Every mask and eps may be NULL (ones / zeros).  Domain: 0 <= n_vae <= n, zdim >= 1; ls_raw,
+ *   mu and sigma may be NULL only when n_vae == 0. */
+int uad_op_reparam_fwd(int n, int n_vae, int zdim, const float* mu_raw, const float* ls_raw, const float* mask_mu, const float* mask_ls,
+                       const float* mask_mu_ce, const float* eps, float* mu, float* ls, float* sigma, float* z, float* kl, void* stream);
+int uad_op_reparam_bwd(int n, int n_vae, int zdim, const float* dz, const float* mu, const float* sigma, const float* eps, const float* mask_mu,
+                       const float* mask_ls, const float* mask_mu_ce, float inv_batch, float* dmu_raw, float* dls_raw, void* stream);
+/* rec_per_sample[i] = sum_b rec_partial[i][b]; scalars[8] = {rec_scale (Rv + Rc), K, Rv + K + Rc, 0, Rv, Rc, Rv + K, 0} * inv_batch with Rv / Rc the sums over
+ * samples [0, n_vae) / [n_vae, n) and K = sum kl[0 .. n_vae) (kl NULL: 0).  One workgroup. */
+int uad_op_loss_finalize(const float* rec_partial, int n, int n_vae, int bps, const float* kl, float inv_batch, float rec_scale, float* rec_per_sample,
+                         float* scalars, void* stream);
+/* Data gradient of the first conv layer (CB = 1): acc[pixel] = sum g[n, i, j, :] . W[ky, kx, 0, :] over the small pixels whose window covers it.  Epilogues:
+ *   plain       (x, dxhat NULL):  dx = acc;
+ *   anomaly map (x, x_hat given): gx = acc + sign(x - x_hat) * inv_batch (sign(0) = 0), dx = gx, anomaly = |x - x_hat| |gx| (either may be NULL, not both);
+ *   restoration (dxhat given):    gx = acc - dxhat, dx = gx (optional), x_upd -= restore_lr * gx in place (optional, not both NULL).
+ * form 0: the launcher's choice; form 1: the one-thread-per-pixel kernel even where the tiled kernel takes the shape.  uad_op_conv_first_dgrad_form returns
+ * the kernel that runs: 2 tiled (k5 s2 P 1, CS 32, HB = 2 HS and WB = 2 WS multiples of 16, N <= 65535), 1 generic (CS a multiple of 8, its KS KS CS
+ * weights within 64 KiB of LDS), 0 neither (the entry then returns UAD_ERR_UNSUPPORTED). */
+int uad_op_conv_first_dgrad_form(const uad_conv_desc_t* d, int form);
+int uad_op_conv_first_dgrad(const uad_conv_desc_t* d, const float* g, const float* W, const float* x, const float* x_hat, float inv_batch, float* anomaly,
+                            float* dx, const float* dxhat, float* x_upd, float restore_lr, int form, void* stream);
+/* dxhat = -sign(r) * inv_batch - tv_lambda * dTV/dr at r = x - xh, TV = sum of |r - r_up| + |r - r_left| over [N,H,W] single-channel images; sign(0) = 0. */
+int uad_op_tv_dxhat(const float* x, const float* xh, int N, int H, int W, float inv_batch, float tv_lambda, float* dxhat, void* stream);
+/* TF-1.15 update rules on g * gscale.  kind 1: p -= lr g.  kind 2: s1 = momentum s1 + g, p -= lr s1.  kind 3: s2 = decay s2 + (1 - decay) g^2,
+ * s1 = momentum s1 + lr g / sqrt(s2 + eps), p -= s1.  fault (optional device word): non-zero leaves p, s1 and s2 untouched. */
+int uad_op_optim(int kind, float* p, const float* g, float* s1, float* s2, long long n, float lr, float momentum, float decay, float eps, float gscale,
+                 const unsigned* fault, void* stream);
+/* Spatial latent on [rows, C]: z = mask * lrelu_alpha(gamma * rs0 * c + beta); backward dc = dz * mask * lrelu' * gamma * rs0 and
+ * colpart[B][2][C] = per-block column sums of {d bn, d bn * c}, B = uad_op_spatial_z_bwd_blocks(rows).  Domain: forward C a multiple of 4; backward C / 4 a
+ * power of two <= 256 (its lanes tile a 256-thread workgroup); 16-byte aligned operands. */
+int uad_op_spatial_z_fwd(const float* c, const float* gamma, const float* beta, float rs0, float alpha, const float* mask, int rows, int C, float* z,
+                         void* stream);
+int uad_op_spatial_z_bwd_blocks(int rows);
+int uad_op_spatial_z_bwd(const float* dz, const float* c, const float* gamma, const float* beta, float rs0, float alpha, const float* mask, int rows, int C,
+                         float* dc, float* colpart, void* stream);
+/* out[c] = sum_r g[r][c].  scratch: uad_op_colsum_scratch_floats(rows, C) floats = row chunks x C; one chunk: a single launch writes out and scratch may
+ * be NULL; more: per-chunk sums into scratch, then the library's slab sum. */
+long long uad_op_colsum_scratch_floats(int rows, int C);
+int uad_op_colsum(const float* g, int rows, int C, float* out, float* scratch, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

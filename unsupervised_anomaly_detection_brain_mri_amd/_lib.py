@@ -85,6 +85,14 @@ class UadGradFinish(C.Structure):
                 ('fin_red', C.c_void_p)]
 
 
+class UadFinal(C.Structure):
+    _fields_ = [('N', C.c_int), ('H', C.c_int), ('W', C.c_int), ('C', C.c_int),
+                ('c_last', C.c_void_p), ('scale', C.c_void_p), ('shift', C.c_void_p), ('alpha', C.c_float), ('mult', C.c_float),
+                ('wf', C.c_void_p), ('bf', C.c_void_p), ('x', C.c_void_p),
+                ('x_hat', C.c_void_p), ('l1_map', C.c_void_p), ('rec_partial', C.c_void_p),
+                ('d_c', C.c_void_p), ('red_partial', C.c_void_p), ('inv_batch', C.c_float), ('dxhat_in', C.c_void_p)]
+
+
 # every symbol include/uad_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'uad_last_error': (C.c_char_p, []),
@@ -223,6 +231,23 @@ SYMBOLS = {
                               C.c_float, C.c_float, C.c_float, C.c_void_p]),
     'uad_op_grad_finish_scratch_floats': (C.c_longlong, []),
     'uad_op_grad_finish': (C.c_int, [C.POINTER(UadGradFinish), C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_final_blocks': (C.c_int, [C.c_int, C.c_int]),
+    'uad_op_final': (C.c_int, [C.POINTER(UadFinal), C.c_void_p]),
+    'uad_op_reparam_fwd': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 12),
+    'uad_op_reparam_bwd': (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_op_loss_finalize': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_op_conv_first_dgrad_form': (C.c_int, [C.POINTER(UadConvDesc), C.c_int]),
+    'uad_op_conv_first_dgrad': (C.c_int, [C.POINTER(UadConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
+    'uad_op_tv_dxhat': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'uad_op_optim': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                               C.c_void_p, C.c_void_p]),
+    'uad_op_spatial_z_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_spatial_z_bwd_blocks': (C.c_int, [C.c_int]),
+    'uad_op_spatial_z_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    'uad_op_colsum_scratch_floats': (C.c_longlong, [C.c_int, C.c_int]),
+    'uad_op_colsum': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -226,12 +226,14 @@ void uad_launch_reparam_bwd(int n, int n_vae, int zdim, const float* dz, const f
                             const float* eps, const float* mask_mu, const float* mask_ls, const float* mask_mu_ce,
                             float inv_batch, float* dmu_raw, float* dls_raw, hipStream_t st);
 // ceVAE: data gradient of the first conv (d.N samples) + direct L1-label term -> anomaly = |x-x_hat| * |d loss_vae/dx|
+// generic: run the one-thread-per-pixel kernel even where the tiled form takes the shape (uad_conv_first_dgrad_tiled; op-level tests)
+bool uad_conv_first_dgrad_tiled(const UadConvDesc& d);
 void uad_launch_conv_first_dgrad(const UadConvDesc& d, const float* g, const float* W, const float* x,
-                                 const float* x_hat, float inv_batch, float* anomaly, float* dx, hipStream_t st);
+                                 const float* x_hat, float inv_batch, float* anomaly, float* dx, hipStream_t st, bool generic = false);
 // GMVAE form: gx = (data gradient) - dxhat[pix] (x's direct term is minus the reconstruction's), dx (optional) = gx,
 // and, if x_upd is given, the restoration update x_upd[pix] -= restore_lr * gx (trainers/GMVAE_spatial.py:189-190)
 void uad_launch_conv_first_dgrad_restore(const UadConvDesc& d, const float* g, const float* W, const float* dxhat,
-                                         float* dx, float* x_upd, float restore_lr, hipStream_t st);
+                                         float* dx, float* x_upd, float restore_lr, hipStream_t st, bool generic = false);
 
 // ---- dense bottleneck, one workgroup per sample (uad_bott.hip) ----
 struct UadBottArgs {

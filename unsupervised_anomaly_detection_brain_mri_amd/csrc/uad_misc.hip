@@ -1367,9 +1367,10 @@ static bool first_dgrad_tiled_ok(const UadConvDesc& d) {
     return d.KS == 5 && d.S == 2 && d.P == 1 && d.CB == 1 && d.CS == 32 && d.HB % 16 == 0 && d.WB % 16 == 0 &&
            d.HB == 2 * d.HS && d.WB == 2 * d.WS && d.N <= 65535;
 }
+bool uad_conv_first_dgrad_tiled(const UadConvDesc& d) { return first_dgrad_tiled_ok(d); }
 void uad_launch_conv_first_dgrad(const UadConvDesc& d, const float* g, const float* W, const float* x,
-                                 const float* x_hat, float inv_batch, float* anomaly, float* dx, hipStream_t st) {
-    if (first_dgrad_tiled_ok(d)) {
+                                 const float* x_hat, float inv_batch, float* anomaly, float* dx, hipStream_t st, bool generic) {
+    if (!generic && first_dgrad_tiled_ok(d)) {
         FirstDgradEpi e{x, x_hat, inv_batch, anomaly, dx, nullptr, nullptr, 0.f};
         hipLaunchKernelGGL(conv_first_dgrad_tiled_kernel, dim3(d.WB / 16, d.HB / 16, d.N), dim3(256), 0, st, d, g, W, e);
         return;
@@ -1380,8 +1381,8 @@ void uad_launch_conv_first_dgrad(const UadConvDesc& d, const float* g, const flo
                        (const float*)nullptr, (float*)nullptr, 0.f);
 }
 void uad_launch_conv_first_dgrad_restore(const UadConvDesc& d, const float* g, const float* W, const float* dxhat,
-                                         float* dx, float* x_upd, float restore_lr, hipStream_t st) {
-    if (first_dgrad_tiled_ok(d)) {
+                                         float* dx, float* x_upd, float restore_lr, hipStream_t st, bool generic) {
+    if (!generic && first_dgrad_tiled_ok(d)) {
         FirstDgradEpi e{nullptr, nullptr, 0.f, nullptr, dx, dxhat, x_upd, restore_lr};
         hipLaunchKernelGGL(conv_first_dgrad_tiled_kernel, dim3(d.WB / 16, d.HB / 16, d.N), dim3(256), 0, st, d, g, W, e);
         return;

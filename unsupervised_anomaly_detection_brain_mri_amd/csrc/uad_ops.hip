@@ -3,6 +3,7 @@
 // kernels of the conv layer (uad_conv_plan.hip and its kernel units) / uad_misc.hip on caller-supplied tensors (weight packs and workspace built on the fly, synchronous: tests and
 // tools), and the k3 kernel's in-kernel profile switch.  Host-only: no kernel is defined here.
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -397,6 +398,136 @@ int uad_op_grad_finish(const uad_grad_finish_t* a, int fused, float* scratch, vo
         if (a->slabs) uad_launch_reduce_partials(a->slabs, a->S, a->L, 1.0f, a->dW, st);
         if (a->colpart) uad_launch_bn_grad_finalize(a->colpart, a->T, a->C, a->gamma, a->rstd, a->dgamma, a->dbeta, a->dbias, st, scratch);
     }
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the step's small kernels, one launch each
+// Each entry checks the domain the kernel itself assumes (read from the kernel, csrc/uad_misc.hip) and launches nothing outside it.
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int uad_op_final_blocks(int H, int W) { return (H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) ? 0 : uad_final_blocks_per_sample(H, W); }
+int uad_op_final(const uad_final_t* a, void* stream) {
+    if (!a) return fail(UAD_ERR_INVALID, "final: null argument");
+    if (a->N < 1 || a->H < 1 || a->W < 1 || a->C < 1) return fail(UAD_ERR_INVALID, "final: sizes must be positive");
+    // C / 4 lanes share a pixel and fold their dot product with xor-shuffles (a power of two), the block's 3 C + 2 partials sit in 200 LDS floats
+    const int lpp = a->C / 4;
+    if (a->C % 4 || (lpp & (lpp - 1)) || 3 * a->C + 2 > 200) return fail(UAD_ERR_UNSUPPORTED, "final: C must be 4, 8, 16, 32 or 64 (got %d)", a->C);
+    if (a->N > 65535 || (long long)a->H * a->W > 0x7fffffffLL) return fail(UAD_ERR_UNSUPPORTED, "final: at most 65535 samples of fewer than 2^31 pixels");
+    if (!a->c_last || !a->scale || !a->shift || !a->wf || !a->bf || !a->x || !a->x_hat || !a->rec_partial) return fail(UAD_ERR_INVALID, "final: null input or output");
+    if (a->d_c && !a->red_partial) return fail(UAD_ERR_INVALID, "final: the backward needs red_partial");
+    if (!al16(a->c_last) || !al16(a->scale) || !al16(a->shift) || !al16(a->wf) || !al16(a->d_c)) return fail(UAD_ERR_INVALID, "final: c_last, d_c, scale, shift and wf must be 16-byte aligned");
+    UadFinalArgs f;
+    f.N = a->N; f.H = a->H; f.W = a->W; f.C = a->C;
+    f.c_last = a->c_last; f.scale = a->scale; f.shift = a->shift; f.alpha = a->alpha; f.mult = a->mult;
+    f.wf = a->wf; f.bf = a->bf; f.x = a->x; f.x_hat = a->x_hat; f.l1_map = a->l1_map; f.rec_partial = a->rec_partial;
+    f.d_c = a->d_c; f.red_partial = a->red_partial; f.inv_batch = a->inv_batch; f.dxhat_in = a->dxhat_in;
+    uad_launch_final_fwd_bwd(f, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_op_reparam_fwd(int n, int n_vae, int zdim, const float* mu_raw, const float* ls_raw, const float* mask_mu, const float* mask_ls,
+                       const float* mask_mu_ce, const float* eps, float* mu, float* ls, float* sigma, float* z, float* kl, void* stream) {
+    if (n < 1 || zdim < 1 || n_vae < 0 || n_vae > n) return fail(UAD_ERR_INVALID, "reparam_fwd: n, zdim >= 1 and 0 <= n_vae <= n");
+    if (!mu_raw || (n_vae > 0 && !ls_raw) || !mu || !ls || !sigma || !z || !kl) return fail(UAD_ERR_INVALID, "reparam_fwd: null input or output");
+    uad_launch_reparam_fwd(n, n_vae, zdim, mu_raw, ls_raw, mask_mu, mask_ls, mask_mu_ce, eps, mu, ls, sigma, z, kl, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+int uad_op_reparam_bwd(int n, int n_vae, int zdim, const float* dz, const float* mu, const float* sigma, const float* eps, const float* mask_mu,
+                       const float* mask_ls, const float* mask_mu_ce, float inv_batch, float* dmu_raw, float* dls_raw, void* stream) {
+    if (n < 1 || zdim < 1 || n_vae < 0 || n_vae > n) return fail(UAD_ERR_INVALID, "reparam_bwd: n, zdim >= 1 and 0 <= n_vae <= n");
+    if (!dz || (n_vae > 0 && (!mu || !sigma)) || !dmu_raw || !dls_raw) return fail(UAD_ERR_INVALID, "reparam_bwd: null input or output");
+    uad_launch_reparam_bwd(n, n_vae, zdim, dz, mu, sigma, eps, mask_mu, mask_ls, mask_mu_ce, inv_batch, dmu_raw, dls_raw, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+int uad_op_loss_finalize(const float* rec_partial, int n, int n_vae, int bps, const float* kl, float inv_batch, float rec_scale, float* rec_per_sample,
+                         float* scalars, void* stream) {
+    if (n < 1 || bps < 1 || n_vae < 0 || n_vae > n) return fail(UAD_ERR_INVALID, "loss_finalize: n, bps >= 1 and 0 <= n_vae <= n");
+    if (!rec_partial || !rec_per_sample || !scalars) return fail(UAD_ERR_INVALID, "loss_finalize: null input or output");
+    uad_launch_loss_finalize(rec_partial, n, n_vae, bps, kl, inv_batch, rec_scale, rec_per_sample, scalars, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+// 2 tiled | 1 generic | 0 neither.  The generic kernel indexes a single input channel, reads the gradient as pairs of float4 and stages KS KS CS weights in LDS.
+static int first_dgrad_form(const UadConvDesc& d, int form) {
+    if (d.N < 1 || d.HB < 1 || d.WB < 1 || d.HS < 1 || d.WS < 1 || d.KS < 1 || d.S < 1 || d.P < 0) return 0;
+    if (!form && uad_conv_first_dgrad_tiled(d)) return 2;
+    if (d.CB != 1 || d.CS < 8 || d.CS % 8 || (size_t)d.KS * d.KS * d.CS * sizeof(float) > 65536) return 0;
+    if (((size_t)d.N * d.HB * d.WB + 255) / 256 > 0x7fffffffull) return 0;
+    return 1;
+}
+int uad_op_conv_first_dgrad_form(const uad_conv_desc_t* d, int form) { return (d && (form == 0 || form == 1)) ? first_dgrad_form(to_desc(d), form) : 0; }
+int uad_op_conv_first_dgrad(const uad_conv_desc_t* dd, const float* g, const float* W, const float* x, const float* x_hat, float inv_batch, float* anomaly,
+                            float* dx, const float* dxhat, float* x_upd, float restore_lr, int form, void* stream) {
+    if (!dd || !g || !W) return fail(UAD_ERR_INVALID, "conv_first_dgrad: null argument");
+    if (form != 0 && form != 1) return fail(UAD_ERR_INVALID, "conv_first_dgrad: form is 0 (the launcher's choice) or 1 (generic kernel)");
+    const UadConvDesc d = to_desc(dd);
+    if (!first_dgrad_form(d, form)) return fail(UAD_ERR_UNSUPPORTED, "conv_first_dgrad: one input channel, Cout a multiple of 8, weights within 64 KiB of LDS");
+    if (!al16(g) || !al16(W)) return fail(UAD_ERR_INVALID, "conv_first_dgrad: g and W must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (dxhat) {
+        if (x || x_hat || anomaly) return fail(UAD_ERR_INVALID, "conv_first_dgrad: the restoration epilogue takes no x, x_hat or anomaly");
+        if (!dx && !x_upd) return fail(UAD_ERR_INVALID, "conv_first_dgrad: the restoration epilogue needs dx or x_upd");
+        uad_launch_conv_first_dgrad_restore(d, g, W, dxhat, dx, x_upd, restore_lr, st, form == 1);
+    } else {
+        if (x_upd) return fail(UAD_ERR_INVALID, "conv_first_dgrad: x_upd needs dxhat");
+        if (x ? (!x_hat || (!dx && !anomaly)) : (x_hat || anomaly || !dx)) return fail(UAD_ERR_INVALID, "conv_first_dgrad: plain form: dx alone; anomaly form: x, x_hat and dx or anomaly");
+        uad_launch_conv_first_dgrad(d, g, W, x, x_hat, inv_batch, anomaly, dx, st, form == 1);
+    }
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_op_tv_dxhat(const float* x, const float* xh, int N, int H, int W, float inv_batch, float tv_lambda, float* dxhat, void* stream) {
+    if (N < 1 || H < 1 || W < 1 || !x || !xh || !dxhat) return fail(UAD_ERR_INVALID, "tv_dxhat: sizes must be positive and pointers non-null");
+    if (((unsigned long long)N * H * W + 255) / 256 > 0x7fffffffull) return fail(UAD_ERR_UNSUPPORTED, "tv_dxhat: too many pixels for one launch");
+    uad_launch_tv_dxhat(x, xh, N, H, W, inv_batch, tv_lambda, dxhat, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_op_optim(int kind, float* p, const float* g, float* s1, float* s2, long long n, float lr, float momentum, float decay, float eps, float gscale,
+                 const unsigned* fault, void* stream) {
+    if (kind < 1 || kind > 3) return fail(UAD_ERR_UNSUPPORTED, "optim: kind is 1 (SGD), 2 (Momentum) or 3 (RMSProp); Adam is uad_op_adam");
+    if (n < 1 || !p || !g || (kind >= 2 && !s1) || (kind == 3 && !s2)) return fail(UAD_ERR_INVALID, "optim: n >= 1, p, g and the slots of the kind (2: s1; 3: s1, s2)");
+    if ((n + 255) / 256 > 0x7fffffffLL) return fail(UAD_ERR_UNSUPPORTED, "optim: too many elements for one launch");
+    uad_launch_optim(kind, p, g, s1, s2, (size_t)n, lr, momentum, decay, eps, gscale, (hipStream_t)stream, fault);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+int uad_op_spatial_z_fwd(const float* c, const float* gamma, const float* beta, float rs0, float alpha, const float* mask, int rows, int C, float* z,
+                         void* stream) {
+    if (rows < 1 || C < 1 || !c || !gamma || !beta || !z) return fail(UAD_ERR_INVALID, "spatial_z_fwd: sizes must be positive and pointers non-null");
+    if (C % 4) return fail(UAD_ERR_UNSUPPORTED, "spatial_z_fwd: C must be a multiple of 4 (got %d)", C);
+    if (!al16(c) || !al16(gamma) || !al16(beta) || !al16(mask) || !al16(z)) return fail(UAD_ERR_INVALID, "spatial_z_fwd: operands must be 16-byte aligned");
+    uad_launch_spatial_z_fwd(c, gamma, beta, rs0, alpha, mask, rows, C, z, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+int uad_op_spatial_z_bwd_blocks(int rows) { return rows < 1 ? 0 : uad_spatial_z_bwd_blocks(rows); }
+int uad_op_spatial_z_bwd(const float* dz, const float* c, const float* gamma, const float* beta, float rs0, float alpha, const float* mask, int rows, int C,
+                         float* dc, float* colpart, void* stream) {
+    if (rows < 1 || C < 1 || !dz || !c || !gamma || !beta || !dc || !colpart) return fail(UAD_ERR_INVALID, "spatial_z_bwd: sizes must be positive and pointers non-null");
+    // thread = (row lane, channel quad): the C / 4 quads must tile the 256 threads, or a row lane's LDS slot [rl][C] is summed from the wrong rows (C = 48)
+    const int Q = C / 4;
+    if (C % 4 || Q > 256 || (Q & (Q - 1))) return fail(UAD_ERR_UNSUPPORTED, "spatial_z_bwd: C / 4 must be a power of two <= 256 (got C = %d)", C);
+    if (!al16(dz) || !al16(c) || !al16(gamma) || !al16(beta) || !al16(mask) || !al16(dc)) return fail(UAD_ERR_INVALID, "spatial_z_bwd: operands must be 16-byte aligned");
+    uad_launch_spatial_z_bwd(dz, c, gamma, beta, rs0, alpha, mask, rows, C, dc, colpart, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return UAD_OK;
+}
+
+long long uad_op_colsum_scratch_floats(int rows, int C) { return (rows < 1 || C < 1) ? 0 : (long long)uad_colsum_scratch_floats(rows, C); }
+int uad_op_colsum(const float* g, int rows, int C, float* out, float* scratch, void* stream) {
+    if (rows < 1 || C < 1 || !g || !out) return fail(UAD_ERR_INVALID, "colsum: sizes must be positive and pointers non-null");
+    if ((C + 31) / 32 > 0x7fffffff / 32) return fail(UAD_ERR_UNSUPPORTED, "colsum: too many columns for one launch");
+    if (uad_colsum_scratch_floats(rows, C) > (size_t)C && !scratch) return fail(UAD_ERR_INVALID, "colsum: more than one row chunk needs the scratch (uad_op_colsum_scratch_floats)");
+    uad_launch_colsum(g, rows, C, out, scratch, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
