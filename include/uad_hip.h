@@ -799,7 +799,8 @@ typedef struct {
 long long uad_op_grad_finish_scratch_floats(void);
 int uad_op_grad_finish(const uad_grad_finish_t* a, int fused, float* scratch, void* stream);
 
-/* ---- the step's small kernels, ONE launch each on caller-supplied tensors (csrc/uad_misc.hip; uad_op_tv_dxhat: csrc/uad_gmvae.hip) ----
+/* ---- the step's small kernels, ONE launch each on caller-supplied tensors (csrc/uad_loss.hip; the first-layer data gradient: csrc/uad_conv_first.hip;
+ * uad_op_optim: csrc/uad_optim.hip; uad_op_colsum: csrc/uad_reduce.hip; uad_op_tv_dxhat: csrc/uad_gmvae.hip) ----
  * Each entry runs the launcher the engines run, asynchronously on `stream`, and allocates nothing.  Outside the kernel's domain (stated per entry) it
  * launches nothing and returns UAD_ERR_INVALID (a NULL pointer that is needed, a size below 1, a misaligned vector operand) or UAD_ERR_UNSUPPORTED (a
  * width or count no kernel form takes).

@@ -1,4 +1,4 @@
-"""Plain numpy statements of the train / restore step's small kernels (csrc/uad_misc.hip, tv_dxhat_kernel of csrc/uad_gmvae.hip) and the case tables of
+"""Plain numpy statements of the train / restore step's small kernels (csrc/uad_loss.hip, uad_conv_first.hip, uad_optim.hip, uad_reduce.hip; tv_dxhat_kernel of csrc/uad_gmvae.hip) and the case tables of
 tests/test_gpu_step_kernels.py.  tests/test_step_kernel_refs.py pins every statement here against oracle/nn.py and oracle/vae.py without a GPU.
 
 Every ref_* function computes in the precision `dt` it is given (float64: the reference; float32: the same expressions in fp32 arithmetic, dot products

@@ -1,4 +1,4 @@
-"""GPU: the one-launch gradient finish of the train step's side stream (uad_launch_grad_finish, csrc/uad_misc.hip) against the separate launches it
+"""GPU: the one-launch gradient finish of the train step's side stream (uad_launch_grad_finish, csrc/uad_reduce.hip) against the separate launches it
 replaces -- slab sum (reduce_partials*), BN / bias finalize (bn_grad_finalize*), and for the last decoder block the column sum of the fused loss
 epilogue's partials + final_gradfin -- through uad_op_grad_finish(fused = 1 | 0).
 

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, 'libuad_hip.so')
-SOURCES = ['uad_gemm_d16s3.hip', 'uad_gemm_d16s.hip', 'uad_conv_k3.hip', 'uad_conv5_f.hip', 'uad_conv5_d.hip', 'uad_conv5_w.hip', 'uad_gemm.hip', 'uad_conv_plan.hip', 'uad_misc.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_hist.hip', 'uad_confusion.hip', 'uad_moments.hip', 'uad_flow.hip', 'uad_resize.hip', 'uad_cc.hip', 'uad_crops.hip', 'uad_batch.hip', 'uad_render.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_ops.hip', 'uad_allreduce.hip']
+SOURCES = ['uad_gemm_d16s3.hip', 'uad_gemm_d16s.hip', 'uad_conv_k3.hip', 'uad_conv5_f.hip', 'uad_conv5_d.hip', 'uad_conv5_w.hip', 'uad_gemm.hip', 'uad_conv_plan.hip', 'uad_reduce.hip', 'uad_conv_first.hip', 'uad_loss.hip', 'uad_optim.hip', 'uad_batch_io.hip', 'uad_gmvae.hip', 'uad_gmd.hip', 'uad_bott.hip', 'uad_eval.hip', 'uad_resample.hip', 'uad_select.hip', 'uad_hist.hip', 'uad_confusion.hip', 'uad_moments.hip', 'uad_flow.hip', 'uad_resize.hip', 'uad_cc.hip', 'uad_crops.hip', 'uad_batch.hip', 'uad_render.hip', 'uad_gan.hip', 'uad_model.hip', 'uad_ops.hip', 'uad_allreduce.hip']
 ARCH = 'gfx950'
 # per-file flags.  uad_flow.hip must return the bits of utils/curvature_flow.py, uad_resize.hip those of utils/resize.py and uad_render.hip those of
 # utils/render.py: no multiply-add may be fused, in host or device code; uad_hist.hip's centred squares are added as tests/native/hist_emu.cpp adds them;

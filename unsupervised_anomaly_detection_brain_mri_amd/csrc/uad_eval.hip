@@ -3,7 +3,8 @@
 //   * 5x5x5 median filter of a residual volume (scipy default boundary: reflect),
 //   * exact AUROC / AUPRC / Dice-at-threshold over tens of millions of voxels from ONE descending sort
 //     (sklearn's definitions: distinct-score thresholds; the reference sorts on the host for AUPRC and re-thresholds the
-//     whole array ~170 times for the Dice search).
+//     whole array ~170 times for the Dice search),
+//   * the residual anomaly map itself (residual_kernel, uad_launch_residual: the launch layer's internal interface).
 // All of it is HBM-bound integer / order-statistic work: coalesced loads, LDS tiles, no matrix cores.
 // Round 6: the sort, the prefix sums and the compaction are this file's own kernels (an 8-bit-digit LSD radix sort with wave-ballot ranking,
 // a three-phase scan, a flag compaction) -- no library primitives.
@@ -399,7 +400,37 @@ __global__ void __launch_bounds__(256) cc_filter_kernel(const float* __restrict_
     out[v] = count > maxv ? val : 0.f;
 }
 
+// residual anomaly map, one block row per sample (utils/Evaluation.py:282-289)
+__global__ void __launch_bounds__(256) residual_kernel(const float* __restrict__ x, const float* __restrict__ xr,
+                                                       const float* __restrict__ mask, int hw, int pos_only,
+                                                       float prior, float* __restrict__ out,
+                                                       float* __restrict__ l1part) {
+    __shared__ float red[4];
+    const int n = blockIdx.y;
+    float acc = 0.f;
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += gridDim.x * 256) {
+        const size_t i = (size_t)n * hw + p;
+        const float xv = x[i], d = xv - xr[i];
+        acc += fabsf(d);
+        float r = pos_only ? fmaxf(d, 0.f) : fabsf(d);
+        if (mask) r *= mask[i];
+        if (xv < prior) r = 0.f;
+        out[i] = r;
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0 && l1part) l1part[(size_t)n * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
 }  // namespace
+
+void uad_launch_residual(const float* x, const float* xr, const float* mask, int n, int hw, int pos_only,
+                         float prior_thresh, float* out, float* l1err, hipStream_t st) {
+    // one block per sample keeps the per-sample |x - xr| sum a single deterministic partial
+    hipLaunchKernelGGL(residual_kernel, dim3(1, n), dim3(256), 0, st, x, xr, mask, hw, pos_only, prior_thresh, out,
+                       l1err);
+}
 
 struct uad_scores {
     unsigned long long n;

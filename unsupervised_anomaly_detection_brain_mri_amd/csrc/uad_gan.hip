@@ -1,7 +1,7 @@
 // f-AnoGAN (unified graph) on gfx950: LayerNorm-HW kernels (forward, backward, and the second-order backward the WGAN-GP
 // penalty needs), the small heads / losses, and the orchestration of the three optimisation phases behind the C-ABI
 // (include/uad_hip.h, uad_gan_*).  The k5 s2 convolutions, their data and filter gradients, the dense layers and Adam are
-// the kernels of the conv layer (uad_conv_plan.hip and its kernel units) / uad_misc.hip.  The handle's tensor table, flat buffers and packs are the UadHandleCore of uad_handle.h,
+// the kernels of the conv layer (uad_conv_plan.hip and its kernel units) / uad_optim.hip.  The handle's tensor table, flat buffers and packs are the UadHandleCore of uad_handle.h,
 // shared with the AE / VAE-family handle (uad_model.hip).
 //
 // Graph restated (reference): models/fanogan.py:11-84, models/customlayers.py:16-38 (use_batchnorm=False branches),

@@ -153,6 +153,7 @@ void uad_launch_conv_w(const UadConvDesc& d, const float* big, UadXform xfb, con
 // math mode has to be the launch's: the k5 kernels split differently in the two modes
 void uad_launch_conv_w_reduce(const UadConvDesc& d, float* dW, float* partial, hipStream_t st, bool math_bf16x3);
 
+// ---- slab reductions, BN / bias gradient finalize, one-launch gradient finish, column sum (uad_reduce.hip) ----
 // out[j] = scale * sum_{s<S} partial[s*L + j]
 void uad_launch_reduce_partials(const float* partial, int S, int L, float scale, float* out, hipStream_t st);
 // dbeta = S1, dgamma = rstd*S2, dbias = gamma*rstd*S1 with S1,S2 = sum over T tiles of colpart[t][0/1][c]
@@ -186,14 +187,25 @@ constexpr size_t kUadColsumScratchFloats = 64 * 1024;
 void uad_launch_colsum(const float* g, int rows, int C, float* out, float* scratch, hipStream_t st);
 size_t uad_colsum_scratch_floats(int rows, int C);
 
-// first layer (tiny Cin, raw image input): direct conv + bias, and its weight gradient
+// ---- first layer (tiny Cin, raw image input): direct conv + bias, its weight gradient and its data gradient (uad_conv_first.hip) ----
 void uad_launch_conv_first_fwd(const UadConvDesc& d, const float* x, const float* W, const float* bias,
                                float* out, hipStream_t st);
 size_t uad_conv_first_wgrad_partial_floats(const UadConvDesc& d);
 void uad_launch_conv_first_wgrad(const UadConvDesc& d, const float* x, const float* g, float* dW,
                                  float* partial, hipStream_t st);
+// ceVAE: data gradient of the first conv (d.N samples) + direct L1-label term -> anomaly = |x-x_hat| * |d loss_vae/dx|
+// generic: run the one-thread-per-pixel kernel even where the tiled form takes the shape (uad_conv_first_dgrad_tiled; op-level tests)
+bool uad_conv_first_dgrad_tiled(const UadConvDesc& d);
+void uad_launch_conv_first_dgrad(const UadConvDesc& d, const float* g, const float* W, const float* x,
+                                 const float* x_hat, float inv_batch, float* anomaly, float* dx, hipStream_t st, bool generic = false);
+// GMVAE form: gx = (data gradient) - dxhat[pix] (x's direct term is minus the reconstruction's), dx (optional) = gx,
+// and, if x_upd is given, the restoration update x_upd[pix] -= restore_lr * gx (trainers/GMVAE_spatial.py:189-190)
+void uad_launch_conv_first_dgrad_restore(const UadConvDesc& d, const float* g, const float* W, const float* dxhat,
+                                         float* dx, float* x_upd, float restore_lr, hipStream_t st, bool generic = false);
+// dx = data gradient of the first conv, nothing else (f-AnoGAN critic input gradient)
+void uad_launch_conv_first_dgrad_plain(const UadConvDesc& d, const float* g, const float* W, float* dx, hipStream_t st);
 
-// final 1x1 conv (C -> 1) fused with the L1 loss and its backward
+// ---- loss side: final 1x1 conv (C -> 1) fused with the L1 loss and its backward, reparameterisation / KL, loss finalize, spatial latent (uad_loss.hip) ----
 struct UadFinalArgs {
     int N, H, W, C;          // c_last is [N,H,W,C]
     const float* c_last;     // pre-BN output of the last ConvT
@@ -225,15 +237,15 @@ void uad_launch_reparam_fwd(int n, int n_vae, int zdim, const float* mu_raw, con
 void uad_launch_reparam_bwd(int n, int n_vae, int zdim, const float* dz, const float* mu, const float* sigma,
                             const float* eps, const float* mask_mu, const float* mask_ls, const float* mask_mu_ce,
                             float inv_batch, float* dmu_raw, float* dls_raw, hipStream_t st);
-// ceVAE: data gradient of the first conv (d.N samples) + direct L1-label term -> anomaly = |x-x_hat| * |d loss_vae/dx|
-// generic: run the one-thread-per-pixel kernel even where the tiled form takes the shape (uad_conv_first_dgrad_tiled; op-level tests)
-bool uad_conv_first_dgrad_tiled(const UadConvDesc& d);
-void uad_launch_conv_first_dgrad(const UadConvDesc& d, const float* g, const float* W, const float* x,
-                                 const float* x_hat, float inv_batch, float* anomaly, float* dx, hipStream_t st, bool generic = false);
-// GMVAE form: gx = (data gradient) - dxhat[pix] (x's direct term is minus the reconstruction's), dx (optional) = gx,
-// and, if x_upd is given, the restoration update x_upd[pix] -= restore_lr * gx (trainers/GMVAE_spatial.py:189-190)
-void uad_launch_conv_first_dgrad_restore(const UadConvDesc& d, const float* g, const float* W, const float* dxhat,
-                                         float* dx, float* x_upd, float restore_lr, hipStream_t st, bool generic = false);
+// scalars[8] = {reconstructionLoss, kl, loss, 0, Rec_vae, Rec_ce, loss_vae, 0}; samples [n_vae, n) = ceVAE context branch
+void uad_launch_loss_finalize(const float* rec_partial, int n, int n_vae, int bps, const float* kl_per_sample,
+                              float inv_batch, float rec_scale, float* rec_per_sample, float* scalars, hipStream_t st);
+// spatial autoencoder latent: z = mask * lrelu(gamma * rs0 * c + beta) and its backward (colpart [blocks][2][C], blocks as returned)
+void uad_launch_spatial_z_fwd(const float* c, const float* gamma, const float* beta, float rs0, float alpha, const float* mask, int rows,
+                              int C, float* z, hipStream_t st);
+int uad_spatial_z_bwd_blocks(int rows);
+void uad_launch_spatial_z_bwd(const float* dz, const float* c, const float* gamma, const float* beta, float rs0, float alpha,
+                              const float* mask, int rows, int C, float* dc, float* colpart, hipStream_t st);
 
 // ---- dense bottleneck, one workgroup per sample (uad_bott.hip) ----
 struct UadBottArgs {
@@ -348,30 +360,22 @@ struct UadGmdArgs {
 size_t uad_gmd_lds_bytes(int W, int Z, int C);
 void uad_launch_gmd_fwd(const UadGmdArgs& a, int n, hipStream_t st);
 void uad_launch_gmd_bwd(const UadGmdArgs& a, int n, hipStream_t st);
-// dx = data gradient of the first conv, nothing else (f-AnoGAN critic input gradient)
-void uad_launch_conv_first_dgrad_plain(const UadConvDesc& d, const float* g, const float* W, float* dx, hipStream_t st);
-// spatial autoencoder latent: z = mask * lrelu(gamma * rs0 * c + beta) and its backward (colpart [blocks][2][C], blocks as returned)
-void uad_launch_spatial_z_fwd(const float* c, const float* gamma, const float* beta, float rs0, float alpha, const float* mask, int rows,
-                              int C, float* z, hipStream_t st);
-int uad_spatial_z_bwd_blocks(int rows);
-void uad_launch_spatial_z_bwd(const float* dz, const float* c, const float* gamma, const float* beta, float rs0, float alpha,
-                              const float* mask, int rows, int C, float* dc, float* colpart, hipStream_t st);
+
+// ---- batch gather, mask multiply, noise fill, clock probe (uad_batch_io.hip) ----
 // batch assembly from the HBM-resident slice cache: out[b] = src[idx[b]]; mask[b][p] = lut[labels[idx[b]][p]] (lut null: the label value)
-// counter-based noise of one step (uad_misc.hip: rng_fill_kernel); at most 8 jobs
-struct UadRngJob { float* out; int per_sample; int kind; float rate; int stream; };
-void uad_launch_rng_fill(const UadRngJob* jobs, int njobs, int n, unsigned long long seed, unsigned long long step, long long sample0,
-                         hipStream_t st);
-// shader-clock probe: one wave samples s_memtime / s_memrealtime for `ticks` 100 MHz ticks (uad_misc.hip: clock_probe_kernel)
-void uad_launch_clock_probe(unsigned long long* out, unsigned long long ticks, hipStream_t st);
 void uad_launch_gather_slices(const float* src, const int* idx, int n, long long slice_elems, float* out, hipStream_t st);
 void uad_launch_gather_mask(const unsigned char* labels, const int* idx, int n, long long slice_px, const unsigned char* lut,
                             float* out, hipStream_t st);
+// counter-based noise of one step (rng_fill_kernel); at most 8 jobs
+struct UadRngJob { float* out; int per_sample; int kind; float rate; int stream; };
+void uad_launch_rng_fill(const UadRngJob* jobs, int njobs, int n, unsigned long long seed, unsigned long long step, long long sample0,
+                         hipStream_t st);
+// shader-clock probe: one wave samples s_memtime / s_memrealtime for `ticks` 100 MHz ticks (clock_probe_kernel)
+void uad_launch_clock_probe(unsigned long long* out, unsigned long long ticks, hipStream_t st);
 // y = x * mask (mask may be null -> copy)
 void uad_launch_mul(const float* x, const float* mask, float* y, size_t n, hipStream_t st);
-// scalars[8] = {reconstructionLoss, kl, loss, 0, Rec_vae, Rec_ce, loss_vae, 0}; samples [n_vae, n) = ceVAE context branch
-void uad_launch_loss_finalize(const float* rec_partial, int n, int n_vae, int bps, const float* kl_per_sample,
-                              float inv_batch, float rec_scale, float* rec_per_sample, float* scalars, hipStream_t st);
 
+// ---- optimizers (uad_optim.hip) ----
 // TF-form Adam over a flat parameter buffer: g is multiplied by gscale first
 // fault (optional, device word): non-zero = the gradients of this step are invalid (fused bottleneck: UadBottArgs::err_dev) -> the kernel leaves
 // parameters and slots untouched
@@ -380,13 +384,22 @@ void uad_launch_optim(int kind, float* p, const float* g, float* s1, float* s2, 
 void uad_launch_adam(float* p, const float* g, float* m, float* v, size_t n, float lr_t, float beta1, float beta2,
                      float eps, float gscale, hipStream_t st, const unsigned* fault = nullptr);
 
-// residual anomaly map (utils/Evaluation.py:282-289): out = mask * (pos_only ? max(x-xr,0) : |x-xr|),
+// ---- residual anomaly map (uad_eval.hip) ----
+// (utils/Evaluation.py:282-289): out = mask * (pos_only ? max(x-xr,0) : |x-xr|),
 // zeroed where x < prior_thresh (pass -inf to disable); per-sample sum|x-xr| into l1err[n] (may be null)
 void uad_launch_residual(const float* x, const float* xr, const float* mask, int n, int hw, int pos_only,
                          float prior_thresh, float* out, float* l1err, hipStream_t st);
+
+// ---- device helper shared by the kernel units ----
+// sum over the 64 lanes of a wavefront, every lane gets it (xor butterfly: a fixed order)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 #endif  // UAD_HOST_EMULATION
 
-// ---- the counter-based generator of uad_rng_fill (uad_misc.hip: rng_fill_kernel) and uad_assemble_batch (uad_batch.hip) ----
+// ---- the counter-based generator of uad_rng_fill (uad_batch_io.hip: rng_fill_kernel) and uad_assemble_batch (uad_batch.hip) ----
 // Philox4x32-10 keyed by the run seed; oracle/rng.py is the CPU statement.  Inline, so that both kernels form the same bits.
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
 #pragma unroll

@@ -1,6 +1,6 @@
 // The part of the C-ABI (include/uad_hip.h) that takes no model handle: the library's error message and version, the stand-alone device ops
 // (residual, counter-based random fill, clock probe, slice / mask gathers), the op-level entry points uad_op_* that run ONE launch of the
-// kernels of the conv layer (uad_conv_plan.hip and its kernel units) / uad_misc.hip on caller-supplied tensors (weight packs and workspace built on the fly, synchronous: tests and
+// kernels of the conv layer (uad_conv_plan.hip and its kernel units) / of the step's small-kernel units (uad_reduce.hip, uad_conv_first.hip, uad_loss.hip, uad_optim.hip) on caller-supplied tensors (weight packs and workspace built on the fly, synchronous: tests and
 // tools), and the k3 kernel's in-kernel profile switch.  Host-only: no kernel is defined here.
 #include <stdarg.h>
 #include <stdint.h>
@@ -403,7 +403,7 @@ int uad_op_grad_finish(const uad_grad_finish_t* a, int fused, float* scratch, vo
 }
 
 // ------------------------------------------------------------------------------------------------ the step's small kernels, one launch each
-// Each entry checks the domain the kernel itself assumes (read from the kernel, csrc/uad_misc.hip) and launches nothing outside it.
+// Each entry checks the domain the kernel itself assumes (read from the kernel: csrc/uad_loss.hip, uad_conv_first.hip, uad_optim.hip, uad_reduce.hip) and launches nothing outside it.
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int uad_op_final_blocks(int H, int W) { return (H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) ? 0 : uad_final_blocks_per_sample(H, W); }
