@@ -861,6 +861,70 @@ int uad_op_spatial_z_bwd(const float* dz, const float* c, const float* gamma, co
 long long uad_op_colsum_scratch_floats(int rows, int C);
 int uad_op_colsum(const float* g, int rows, int C, float* out, float* scratch, void* stream);
 
+/* ---- the small kernels of the materialised-graph engine (csrc/uad_gan_kernels.inc; entries in csrc/uad_gan_ops.inc), ONE launch each on caller-supplied
+ * tensors through the launch helper the uad_gan_* phases use.  Asynchronous on `stream`, nothing is allocated.  Outside the kernel's domain an entry launches
+ * nothing and returns UAD_ERR_INVALID (a NULL tensor that is needed, an extent below 1, a misaligned float4 operand, an unknown kind / mode / rule) or
+ * UAD_ERR_UNSUPPORTED (a width or count the kernel does not take).  Tensors are row-major [rows, C] unless stated; "float4 operand" = 16-byte aligned.
+ *
+ * Row-split kernels (bn_act_bwd, coef_colsum, gfinal_bwd): `rows` rows go to B = uad_op_gan_rows_blocks(rows, max_blocks) workgroups of ceil(rows /
+ *   max_blocks) consecutive rows; max_blocks is one of the engine's rules 256 (coef_colsum), 512 (bn_act_bwd), 1024 (gfinal_bwd).  Each of the C / 4 channel
+ *   quads gets 256 / (C / 4) row lanes: C / 4 must divide 256 and C <= 1024.
+ * uad_op_gan_bn_act_fwd: a = lrelu_alpha(c * (gamma * rs0) + beta).  C a multiple of 4.
+ * uad_op_gan_bn_act_bwd: dn = da * lrelu'(c * (gamma * rs0) + beta), dc = dn * (gamma * rs0), colpart[B][2][C] = per-workgroup column sums of {dn, dn * c}.
+ *   C <= 256 in addition (one thread per channel writes the partials).
+ * uad_op_gan_rowdot: out[row] = act(feat[row, :] . w + b[0]), act 0 none | 1 sigmoid | 2 tanh.  min(C / 4, 64) lanes per row, a power of two.
+ * uad_op_gan_topgrad: out[row, :] = coef4[row / rows_per_group] * w.  rows <= 4 rows_per_group, C a multiple of 4.
+ * uad_op_gan_coef_colsum: partial[B][C] = per-workgroup sums of coef4[row / rows_per_group] * feat[row, :].  rows <= 4 rows_per_group.
+ * uad_op_gan_gfinal_bwd: dv = dx[row] * (act 0: x (1 - x) | 1: 1 - x^2 | 2: 1), da[row, :] = dv * wf; with partial: partial[B][C + 1] = per-workgroup sums of
+ *   {dv * a[row, :], dv}, and then C <= 256. */
+int uad_op_gan_rows_blocks(int rows, int max_blocks);
+int uad_op_gan_bn_act_fwd(const float* c, const float* gamma, const float* beta, float rs0, float alpha, long long rows, int C, float* a, void* stream);
+int uad_op_gan_bn_act_bwd(const float* da, const float* c, const float* gamma, const float* beta, float rs0, float alpha, int rows, int C, int max_blocks,
+                          float* dc, float* colpart, void* stream);
+int uad_op_gan_rowdot(int act, const float* feat, const float* w, const float* b, int rows, int C, float* out, void* stream);
+int uad_op_gan_topgrad(const float* w, long long rows, int rows_per_group, int C, const float* coef4, float* out, void* stream);
+int uad_op_gan_coef_colsum(const float* feat, int rows, int rows_per_group, int C, const float* coef4, int max_blocks, float* partial, void* stream);
+int uad_op_gan_gfinal_bwd(const float* dx, const float* x, const float* a, const float* wf, int rows, int C, int act, int max_blocks, float* da,
+                          float* partial, void* stream);
+/* din [3][n, HW] = {xg, x, x + alpha[sample] * (xg - x)}. */
+int uad_op_gan_interp(const float* xg, const float* x, const float* alpha, int n, int HW, float* din, void* stream);
+/* Elementwise kernels over n floats.  TANH: out = tanh(a).  TANH_BWD: out = a * (1 - b^2) * (c ? c : 1)  (a = dz, b = z, c = optional mask).
+ * DIFF_SCALE: out = coef * (a - b); _ACC: out += coef * (a - b).  SIGN_SCALE: out = coef * sign(a - b), sign(0) = 0.  ADD: out += a.  ADD_SCALAR: out += b[0].
+ * LRELU_FWD: out = a > 0 ? a : coef * a.  LRELU_BWD: out = b > 0 ? a : coef * a  (a = d / d activation, b = pre-activation); both: n a multiple of 4,
+ * float4 operands. */
+enum { UAD_GAN_FLAT_TANH = 0, UAD_GAN_FLAT_TANH_BWD = 1, UAD_GAN_FLAT_DIFF_SCALE = 2, UAD_GAN_FLAT_DIFF_SCALE_ACC = 3, UAD_GAN_FLAT_SIGN_SCALE = 4,
+       UAD_GAN_FLAT_ADD = 5, UAD_GAN_FLAT_ADD_SCALAR = 6, UAD_GAN_FLAT_LRELU_FWD = 7, UAD_GAN_FLAT_LRELU_BWD = 8 };
+int uad_op_gan_flat(int kind, const float* a, const float* b, const float* c, float coef, long long n, float* out, void* stream);
+/* partial[uad_op_gan_sum_blocks()] = per-workgroup sums (fixed grid, grid-stride) of mode 0: a | 1: (a - b)^2 | 2: |a - b|, mode 2 also writing map = |a - b|
+ * when map is given. */
+int uad_op_gan_sum_blocks(void);
+int uad_op_gan_sum(int mode, const float* a, const float* b, long long n, float* map, float* partial, void* stream);
+/* WGAN-GP slope penalty on g [n, H, W]: s[n, W] = sqrt(sum_h g^2), partial[uad_op_gan_pen_col_blocks(n, W)] = per-workgroup sums of (s - 1)^2;
+ * uad_op_gan_pen_grad: out = coef * (s - 1) / s * g. */
+int uad_op_gan_pen_col_blocks(int n, int W);
+int uad_op_gan_pen_col(const float* g, int n, int H, int W, float* s, float* partial, void* stream);
+int uad_op_gan_pen_grad(const float* g, const float* s, float coef, int n, int H, int W, float* out, void* stream);
+/* NHWC square maps, C a multiple of 4, float4 operands.  AVG_FWD: in [N,H,H,C] -> out [N,H/2,H/2,C], 0.25 ((a + b) + (c + d)); AVG_BWD: in [N,H/2,H/2,C] ->
+ * out [N,H,H,C] = 0.25 in; both need an even H.  UP2_FWD: in [N,H,H,C] -> out [N,2H,2H,C] nearest neighbour; UP2_BWD: in [N,2H,2H,C] -> out [N,H,H,C],
+ * (a + b) + (c + d). */
+enum { UAD_GAN_POOL_AVG_FWD = 0, UAD_GAN_POOL_AVG_BWD = 1, UAD_GAN_POOL_UP2_FWD = 2, UAD_GAN_POOL_UP2_BWD = 3 };
+int uad_op_gan_pool(int kind, const float* in, int N, int H, int C, float* out, void* stream);
+/* out[(T - 1 - t) * C + c] = w[t * C + c]; out must not alias w. */
+int uad_op_gan_flip_taps(const float* w, int T, int C, float* out, void* stream);
+/* the derived UAD_GAN_S_* scalars of a phase from its raw means (combine_kernel); phase 0 .. 7, out [16]; scalars the phase does not define are not written. */
+int uad_op_gan_combine(int phase, const float* raw, float kappa, float* out, void* stream);
+/* Latent critic zd -> h1 -> h2 -> 1 (leaky_relu 0.2), one workgroup per sample.  mode 0 (critic step): d_fake, d_real, pen [n] and slab [n][zd h1 + h1 +
+ * h1 h2 + h2 + h2 + 1] = the sample's gradient of d_fake / n - d_real / n + pen; mode 1 (generator step): d_fake and dz_fake [n, zd] = -inv_n d d_fake / d zf,
+ * nothing else is written.  hat_mode 0: z_hat = zr + eps (zr - zf); 1: z_hat = zf + eps (zr - zf).  Domain: zd <= 512, h1, h2 <= 400 (LDS arrays). */
+typedef struct {
+    int zd, h1, h2, mode, hat_mode;
+    const float *W1, *b1, *W2, *b2, *W3, *b3;
+    const float *zf, *zr, *eps;
+    float inv_n, scale;
+    float *d_fake, *d_real, *pen, *slab, *dz_fake;
+} uad_gan_critic_t;
+int uad_op_gan_critic(const uad_gan_critic_t* c, int n, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

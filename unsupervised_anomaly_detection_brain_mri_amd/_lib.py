@@ -93,6 +93,13 @@ class UadFinal(C.Structure):
                 ('d_c', C.c_void_p), ('red_partial', C.c_void_p), ('inv_batch', C.c_float), ('dxhat_in', C.c_void_p)]
 
 
+class UadGanCritic(C.Structure):
+    _fields_ = [('zd', C.c_int), ('h1', C.c_int), ('h2', C.c_int), ('mode', C.c_int), ('hat_mode', C.c_int),
+                ('W1', C.c_void_p), ('b1', C.c_void_p), ('W2', C.c_void_p), ('b2', C.c_void_p), ('W3', C.c_void_p), ('b3', C.c_void_p),
+                ('zf', C.c_void_p), ('zr', C.c_void_p), ('eps', C.c_void_p), ('inv_n', C.c_float), ('scale', C.c_float),
+                ('d_fake', C.c_void_p), ('d_real', C.c_void_p), ('pen', C.c_void_p), ('slab', C.c_void_p), ('dz_fake', C.c_void_p)]
+
+
 # every symbol include/uad_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     'uad_last_error': (C.c_char_p, []),
@@ -248,6 +255,26 @@ SYMBOLS = {
                                        C.c_void_p, C.c_void_p]),
     'uad_op_colsum_scratch_floats': (C.c_longlong, [C.c_int, C.c_int]),
     'uad_op_colsum': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_rows_blocks': (C.c_int, [C.c_int, C.c_int]),
+    'uad_op_gan_bn_act_fwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_bn_act_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    'uad_op_gan_rowdot': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_topgrad': (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    'uad_op_gan_coef_colsum': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_gfinal_bwd': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    'uad_op_gan_interp': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_flat': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_longlong, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_sum_blocks': (C.c_int, []),
+    'uad_op_gan_sum': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_pen_col_blocks': (C.c_int, [C.c_int, C.c_int]),
+    'uad_op_gan_pen_col': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_pen_grad': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_pool': (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_flip_taps': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_combine': (C.c_int, [C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    'uad_op_gan_critic': (C.c_int, [C.POINTER(UadGanCritic), C.c_int, C.c_void_p]),
 }
 
 _lib = None

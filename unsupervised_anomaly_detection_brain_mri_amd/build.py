@@ -40,7 +40,7 @@ def build(force=False, verbose=False):
     objdir = os.path.join(ROOT, 'build', 'uad_hip')
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, 'uad_kernels.h'), os.path.join(CSRC, 'uad_handle.h'), os.path.join(CSRC, 'uad_allreduce.h'), os.path.join(ROOT, 'include', 'uad_hip.h'), os.path.join(CSRC, 'uad_gan_kernels.inc'),
-               os.path.join(CSRC, 'uad_gan_create.inc'), os.path.join(CSRC, 'uad_conv16s.inc'), os.path.join(CSRC, 'uad_convk16.inc'),
+               os.path.join(CSRC, 'uad_gan_create.inc'), os.path.join(CSRC, 'uad_gan_ops.inc'), os.path.join(CSRC, 'uad_conv16s.inc'), os.path.join(CSRC, 'uad_convk16.inc'),
                os.path.join(CSRC, 'uad_gemm_common.h'), os.path.join(CSRC, 'uad_conv_launch.h'), os.path.join(CSRC, 'uad_conv_k3_plan.h'), os.path.join(CSRC, 'uad_gemm_d16s_body.inc')]
     # (the .inc files are textual parts of a unit: uad_gan_*.inc of uad_gan.hip, uad_conv16s.inc / uad_gemm_d16s_body.inc of uad_gemm_d16s*.hip, uad_convk16.inc of uad_conv_k3.hip)
     objs = []

@@ -14,6 +14,7 @@
 //   D  ordinary backward of all 3n samples with pass C's d penalty / d c injected on the x_hat third; each filter gradient
 //      runs once over 4n "samples": the 3n (input, d c) pairs plus pass C's (adjoint, pass-B d c) pairs of the same layer.
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -215,6 +216,89 @@ void rowdot(const float* feat, const float* w, const float* b, int rows, int C, 
     if (lpr > 64) lpr = 64;
     hipLaunchKernelGGL((rowdot_kernel<ACT>), dim3(blocks256((size_t)rows * lpr)), dim3(256), 0, st, feat, w, b, rows, C, lpr, out);
 }
+// ---- the small kernels' grid rules, each written ONCE: the phases below and the handle-less uad_op_gan_* entries (uad_gan_ops.inc) launch through these, on
+// plain device pointers.  The kernels' domains (what C, rows, H ... a launch may carry) are checked by the op entries and, for what a model configuration
+// decides, by uad_gan_create.
+// `rows` rows over at most `max_blocks` workgroups of rpb consecutive rows each: the last workgroup may be shorter, none is empty
+struct RowSplit { int rpb, blocks; };
+inline RowSplit row_split(int rows, int max_blocks) {
+    const int rpb = (rows + max_blocks - 1) / max_blocks;
+    return RowSplit{rpb, (rows + rpb - 1) / rpb};
+}
+constexpr int kBnBwdBlocks = 512, kGfinalBlocks = 1024, kCoefColsumBlocks = 256, kSumBlocks = 256;
+void k_bn_act_fwd(const float* c, const float* gamma, const float* beta, float rs0, float alpha, size_t total4, int C, float* a, hipStream_t st) {
+    hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(blocks256(total4)), dim3(256), 0, st, c, gamma, beta, rs0, alpha, total4, C, a);
+}
+// returns the number of partial rows [2][C] written to colpart
+int k_bn_act_bwd(const float* da, const float* c, const float* gamma, const float* beta, float rs0, float alpha, int rows, int C, float* dc, float* colpart,
+                 int max_blocks, hipStream_t st) {
+    const RowSplit s = row_split(rows, max_blocks);
+    hipLaunchKernelGGL(bn_act_bwd_kernel, dim3(s.blocks), dim3(256), 0, st, da, c, gamma, beta, rs0, alpha, rows, s.rpb, C, dc, colpart);
+    return s.blocks;
+}
+// act: 0 sigmoid, 1 tanh, 2 linear.  Returns the number of partial rows [C + 1] (written when partial != nullptr)
+int k_gfinal_bwd(const float* dx, const float* x, const float* a, const float* wf, int rows, int C, int act, float* da, float* partial, int max_blocks,
+                 hipStream_t st) {
+    const RowSplit s = row_split(rows, max_blocks);
+    hipLaunchKernelGGL(gfinal_bwd_kernel, dim3(s.blocks), dim3(256), 0, st, dx, x, a, wf, rows, s.rpb, C, act, da, partial);
+    return s.blocks;
+}
+int k_coef_colsum(const float* feat, int rows, int rows_per_group, int C, Coef4 cf, float* partial, int max_blocks, hipStream_t st) {
+    const RowSplit s = row_split(rows, max_blocks);
+    hipLaunchKernelGGL(coef_colsum_kernel, dim3(s.blocks), dim3(256), 0, st, feat, rows, s.rpb, rows_per_group, C, cf, partial);
+    return s.blocks;
+}
+void k_topgrad(const float* w, int rows_per_group, int C, size_t rows, Coef4 cf, float* out, hipStream_t st) {
+    const size_t t4 = rows * C / 4;
+    hipLaunchKernelGGL(topgrad_kernel, dim3(blocks256(t4)), dim3(256), 0, st, w, rows_per_group, C, t4, cf, out);
+}
+void k_interp(const float* xg, const float* x, const float* alpha, int HW, size_t total, float* din, hipStream_t st) {
+    hipLaunchKernelGGL(interp_kernel, dim3(blocks256(total)), dim3(256), 0, st, xg, x, alpha, HW, total, din);
+}
+void k_tanh(const float* zr, size_t n, float* z, hipStream_t st) { hipLaunchKernelGGL(tanh_kernel, dim3(blocks256(n)), dim3(256), 0, st, zr, n, z); }
+void k_tanh_bwd(const float* dz, const float* z, const float* mask, size_t n, float* dzr, hipStream_t st) {
+    hipLaunchKernelGGL(tanh_bwd_kernel, dim3(blocks256(n)), dim3(256), 0, st, dz, z, mask, n, dzr);
+}
+template <bool ACC>
+void k_diff_scale(const float* a, const float* b, float coef, size_t n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL((diff_scale_kernel<ACC>), dim3(blocks256(n)), dim3(256), 0, st, a, b, coef, n, out);
+}
+void k_sign_scale(const float* a, const float* b, float coef, size_t n, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(sign_scale_kernel, dim3(blocks256(n)), dim3(256), 0, st, a, b, coef, n, out);
+}
+void k_add(float* out, const float* a, size_t n, hipStream_t st) { hipLaunchKernelGGL(add_kernel, dim3(blocks256(n)), dim3(256), 0, st, out, a, n); }
+void k_add_scalar(float* x, const float* b, size_t n, hipStream_t st) { hipLaunchKernelGGL(add_scalar_kernel, dim3(blocks256(n)), dim3(256), 0, st, x, b, n); }
+// partial[kSumBlocks]: a fixed grid, grid-stride over n
+template <int MODE>
+void k_sum(const float* a, const float* b, size_t n, float* map, float* partial, hipStream_t st) {
+    hipLaunchKernelGGL((sum_kernel<MODE>), dim3(kSumBlocks), dim3(256), 0, st, a, b, n, map, partial);
+}
+// one lane per (sample, column); returns the number of partials written
+int k_pen_col(const float* g, int n, int H, int W, float* s, float* partial, hipStream_t st) {
+    const int blocks = (int)blocks256((size_t)n * W);
+    hipLaunchKernelGGL(pen_col_kernel, dim3(blocks), dim3(256), 0, st, g, n, H, W, s, partial);
+    return blocks;
+}
+void k_pen_grad(const float* g, const float* s, float coef, int H, int W, size_t total, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(pen_grad_kernel, dim3(blocks256(total)), dim3(256), 0, st, g, s, coef, H, W, total, out);
+}
+void k_flip_taps(const float* w, int T, int C, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(flip_taps_kernel, dim3(blocks256((size_t)T * C)), dim3(256), 0, st, w, T, C, out);
+}
+void k_combine(int phase, const float* raw, float kappa, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, phase, raw, kappa, out);
+}
+// x [N,H,H,C] -> y [N,2H,2H,C] and the adjoint g [N,2H,2H,C] -> dx [N,H,H,C]
+void up2_fwd(const float* x, int N, int H, int C, float* y, hipStream_t st) {
+    const size_t t4 = (size_t)N * 4 * H * H * C / 4;
+    hipLaunchKernelGGL(up2_fwd_kernel, dim3(blocks256(t4)), dim3(256), 0, st, x, H, H, C, t4, y);
+}
+void up2_bwd(const float* g, int N, int H, int C, float* dx, hipStream_t st) {
+    const size_t t4 = (size_t)N * H * H * C / 4;
+    hipLaunchKernelGGL(up2_bwd_kernel, dim3(blocks256(t4)), dim3(256), 0, st, g, H, H, C, t4, dx);
+}
+// one workgroup per sample
+void k_critic(const CriticArgs& a, int n, hipStream_t st) { hipLaunchKernelGGL(critic_kernel, dim3(n), dim3(128), 0, st, a); }
 // One-pass LayerNorm forms (uad_gan_kernels.inc: the slice in registers between the statistics and the apply sweep).  Maps of up to 1024 pixels: one
 // workgroup per (sample, 32 channels), with the pixel-lane count the two-pass kernels use for that map (same bits).  Larger maps: Q workgroups per slice
 // that exchange their partial sums once (clustered forms).  UAD_NO_LN1 keeps the two-pass kernels everywhere, UAD_NO_LNQ on the large maps.
@@ -293,25 +377,18 @@ void ln_bwd2(uad_gan* m, const LnBwd2Args& a, int N, hipStream_t st) {
     else hipLaunchKernelGGL((ln_bwd2_kernel<32>), dim3(a.C / 32, N), dim3(256), 0, st, a);
 }
 void bn_act_fwd(uad_gan* m, const Block& L, const float* c, int N, float* a, hipStream_t st) {
-    const size_t total4 = (size_t)N * L.H * L.W * L.C / 4;
-    hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(blocks256(total4)), dim3(256), 0, st, c, P(m, L.gamma), P(m, L.beta),
-                       1.0f / sqrtf(1.0f + kBnEps), kLrelu, total4, L.C, a);
+    k_bn_act_fwd(c, P(m, L.gamma), P(m, L.beta), 1.0f / sqrtf(1.0f + kBnEps), kLrelu, (size_t)N * L.H * L.W * L.C / 4, L.C, a, st);
 }
-constexpr int kBnBwdBlocks = 512;
 void bn_act_bwd(uad_gan* m, const Block& L, const float* da, const float* c, int N, float* dc, hipStream_t st) {
     const float rs0 = 1.0f / sqrtf(1.0f + kBnEps);
-    const int rows = N * L.H * L.W;
-    const int rpb = (rows + kBnBwdBlocks - 1) / kBnBwdBlocks;
-    const int blocks = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(bn_act_bwd_kernel, dim3(blocks), dim3(256), 0, st, da, c, P(m, L.gamma), P(m, L.beta), rs0, kLrelu, rows,
-                       rpb, L.C, dc, m->colpart);
+    const int blocks = k_bn_act_bwd(da, c, P(m, L.gamma), P(m, L.beta), rs0, kLrelu, N * L.H * L.W, L.C, dc, m->colpart, kBnBwdBlocks, st);
     uad_launch_bn_grad_finalize(m->colpart, blocks, L.C, P(m, L.gamma), rs0, Gr(m, L.gamma), Gr(m, L.beta), Gr(m, L.b), st);
 }
 // raw[k] = scale * sum(...)
 template <int MODE>
 void reduce_to(uad_gan* m, int k, const float* a, const float* b, size_t n, float scale, float* map, hipStream_t st) {
-    hipLaunchKernelGGL((sum_kernel<MODE>), dim3(256), dim3(256), 0, st, a, b, n, map, m->redpart);
-    uad_launch_reduce_partials(m->redpart, 256, 1, scale, m->raw + k, st);
+    k_sum<MODE>(a, b, n, map, m->redpart, st);
+    uad_launch_reduce_partials(m->redpart, kSumBlocks, 1, scale, m->raw + k, st);
 }
 
 int refresh_packs(uad_gan* m, hipStream_t st) {
@@ -399,13 +476,13 @@ void enc_forward(uad_gan* m, const float* x, const float* mask_z, int n, hipStre
     uad_launch_conv_f(conv1x1_desc(n, r, r, m->cenc, m->cmid), in, no_xform(), P(m, m->e_cw), m->et, epi_bias(P(m, m->e_cb)), st, nullptr, m->ws);
     uad_launch_conv_f(dense_desc(n, m->flat, m->cfg.zdim), m->et, no_xform(), P(m, m->e_dw), m->zr, epi_bias(P(m, m->e_db), mask_z), st, nullptr, m->ws);
     const size_t nz = (size_t)n * m->cfg.zdim;
-    hipLaunchKernelGGL(tanh_kernel, dim3(blocks256(nz)), dim3(256), 0, st, m->zr, nz, m->z);
+    k_tanh(m->zr, nz, m->z, st);
 }
 // dz = d loss / d z_enc in m->dzbuf; writes every Encoder gradient
 void enc_backward(uad_gan* m, const float* x, const float* mask_z, int n, hipStream_t st) {
     const int r = m->cfg.inter_res, zd = m->cfg.zdim;
     const size_t nz = (size_t)n * zd;
-    hipLaunchKernelGGL(tanh_bwd_kernel, dim3(blocks256(nz)), dim3(256), 0, st, m->dzbuf, m->z, mask_z, nz, m->dzr);
+    k_tanh_bwd(m->dzbuf, m->z, mask_z, nz, m->dzr, st);
     const UadConvDesc dd = dense_desc(n, m->flat, zd), dc1 = conv1x1_desc(n, r, r, m->cenc, m->cmid);
     uad_launch_conv_w(dd, m->et, no_xform(), m->dzr, no_xform(), Gr(m, m->e_dw), m->wpartial, st);
     uad_launch_colsum(m->dzr, n, zd, Gr(m, m->e_db), m->colscratch, st);
@@ -484,9 +561,8 @@ void gen_backward(uad_gan* m, const float* z, const float* mask_g, const float* 
     const int rows = n * LL.H * LL.W;
     float* g = m->Ga; float* gn = m->Gb;
     {
-        const int rpb = (rows + 1023) / 1024, blocks = (rows + rpb - 1) / rpb;
-        hipLaunchKernelGGL(gfinal_bwd_kernel, dim3(blocks), dim3(256), 0, st, dx, m->xg, m->ga[m->G.size()], P(m, m->g_fw), rows, rpb,
-                           LL.C, m->variant == UAD_GAN_ANOVAEGAN ? 2 : 0, g, pg ? m->finpart : nullptr);
+        const int blocks = k_gfinal_bwd(dx, m->xg, m->ga[m->G.size()], P(m, m->g_fw), rows, LL.C, m->variant == UAD_GAN_ANOVAEGAN ? 2 : 0, g,
+                                        pg ? m->finpart : nullptr, kGfinalBlocks, st);
         if (pg) {
             uad_launch_reduce_partials(m->finpart, blocks, LL.C + 1, 1.0f, m->colscratch, st);
             hipMemcpyAsync(Gr(m, m->g_fw), m->colscratch, LL.C * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -579,18 +655,12 @@ void c_decode_backward(uad_gan* m, const float* z, const float* dxh, int n, floa
 // ================================================================================================ AAE family
 // models/constrained_autoencoder.py, adversarial_autoencoder.py, constrained_adversarial_autoencoder.py on materialised activations.
 void bn_fwd(uad_gan* m, long long gamma, long long beta, float alpha, const float* c, size_t rows, int C, float* a, hipStream_t st) {
-    const size_t total4 = rows * C / 4;
-    hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(blocks256(total4)), dim3(256), 0, st, c, P(m, gamma), P(m, beta), 1.0f / sqrtf(1.0f + kBnEps),
-                       alpha, total4, C, a);
+    k_bn_act_fwd(c, P(m, gamma), P(m, beta), 1.0f / sqrtf(1.0f + kBnEps), alpha, rows * C / 4, C, a, st);
 }
 // dc = da * act' * gamma'; column partials into `colpart`; returns the number of partial rows written
 int bn_bwd_partial(uad_gan* m, long long gamma, long long beta, float alpha, const float* da, const float* c, int rows, int C, float* dc,
                    float* colpart, hipStream_t st) {
-    const int rpb = (rows + kBnBwdBlocks - 1) / kBnBwdBlocks;
-    const int blocks = (rows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(bn_act_bwd_kernel, dim3(blocks), dim3(256), 0, st, da, c, P(m, gamma), P(m, beta), 1.0f / sqrtf(1.0f + kBnEps), alpha, rows,
-                       rpb, C, dc, colpart);
-    return blocks;
+    return k_bn_act_bwd(da, c, P(m, gamma), P(m, beta), 1.0f / sqrtf(1.0f + kBnEps), alpha, rows, C, dc, colpart, kBnBwdBlocks, st);
 }
 void bn_finalize(uad_gan* m, const float* colpart, int T, int C, long long gamma, long long beta, long long bias, hipStream_t st) {
     uad_launch_bn_grad_finalize(colpart, T, C, P(m, gamma), 1.0f / sqrtf(1.0f + kBnEps), Gr(m, gamma), Gr(m, beta), bias >= 0 ? Gr(m, bias) : nullptr, st);
@@ -705,9 +775,7 @@ void a_decode_backward(uad_gan* m, const float* z, const float* mask_dec, const 
     const int rows = n * LL.H * LL.W;
     float* g = m->Ga; float* gn = m->Gb;
     {
-        const int rpb = (rows + 1023) / 1024, blocks = (rows + rpb - 1) / rpb;
-        hipLaunchKernelGGL(gfinal_bwd_kernel, dim3(blocks), dim3(256), 0, st, dxh, m->xg, m->ga[m->G.size()], P(m, m->g_fw), rows, rpb, LL.C, 2, g,
-                           pg ? m->finpart : nullptr);
+        const int blocks = k_gfinal_bwd(dxh, m->xg, m->ga[m->G.size()], P(m, m->g_fw), rows, LL.C, 2, g, pg ? m->finpart : nullptr, kGfinalBlocks, st);
         if (pg) {
             uad_launch_reduce_partials(m->finpart, blocks, LL.C + 1, 1.0f, m->colscratch, st);
             hipMemcpyAsync(Gr(m, m->g_fw), m->colscratch, LL.C * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -747,7 +815,7 @@ void a_critic(uad_gan* m, int mode, const float* zf, const float* zr, const floa
     a.W1 = P(m, m->a_w1); a.b1 = P(m, m->a_b1); a.W2 = P(m, m->a_w2); a.b2 = P(m, m->a_b2); a.W3 = P(m, m->a_w3); a.b3 = P(m, m->a_b3);
     a.zf = zf; a.zr = zr; a.eps = eps; a.inv_n = 1.0f / (float)n; a.scale = m->cfg.scale;
     a.d_fake = m->a_crit[0]; a.d_real = m->a_crit[1]; a.pen = m->a_crit[2]; a.slab = m->a_slab; a.dz_fake = m->dzbuf;
-    hipLaunchKernelGGL(critic_kernel, dim3(n), dim3(128), 0, st, a);
+    k_critic(a, n, st);
 }
 
 
@@ -783,7 +851,7 @@ int gmv_phase(uad_gan* m, const uad_gan_io_t* io, const float* x, int n, int wan
         float* scal = io->scalars ? io->scalars : m->scalars_own;
         reduce_to<2>(m, 0, x, m->xg, img, 1.0f / (float)n, io->l1_map, st);                         // mean_p_loss (:58-60)
         for (int k = 0; k < 3; ++k) reduce_to<0>(m, 1 + k, m->gm_loss3 + (size_t)k * m->cfg.max_batch, nullptr, (size_t)n, 1.0f / (float)n, nullptr, st);
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, 5, m->raw, 0.0f, scal);
+        k_combine(5, m->raw, 0.0f, scal, st);
         if (io->reconstruction) HIP_TRY(hipMemcpyAsync(io->reconstruction, m->xg, img * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (io->z_enc) HIP_TRY(hipMemcpyAsync(io->z_enc, m->a_zm, (size_t)n * m->gm_Z * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
@@ -793,7 +861,7 @@ int gmv_phase(uad_gan* m, const uad_gan_io_t* io, const float* x, int n, int wan
         uad_launch_tv_dxhat(x, m->xg, n, H, H, 1.0f, tv, m->gm_dxhat, st);                          // sign(x_hat - x) - tv * dTV/dr, r = x - x_hat
         dxh = m->gm_dxhat;
     } else {
-        hipLaunchKernelGGL(sign_scale_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->xg, x, 1.0f / (float)n, img, m->dxbuf);
+        k_sign_scale(m->xg, x, 1.0f / (float)n, img, m->dxbuf, st);
         dxh = m->dxbuf;
     }
     a_decode_backward(m, m->a_zm, io->mask_g, dxh, n, m->dzbuf, st, !restore);
@@ -848,18 +916,18 @@ int aae_phase(uad_gan* m, int phase, const uad_gan_io_t* io, int n, int want_bac
         } else {
             HIP_TRY(hipMemsetAsync(m->raw + 1, 0, sizeof(float), st));
         }
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, 4, m->raw, m->a_constrained ? m->cfg.rho : 0.0f, scal);
+        k_combine(4, m->raw, m->a_constrained ? m->cfg.rho : 0.0f, scal, st);
         if (want_backward) {
-            hipLaunchKernelGGL((diff_scale_kernel<false>), dim3(blocks256(img)), dim3(256), 0, st, m->xg, io->x, 2.0f / (float)img, img, m->dxbuf);
+            k_diff_scale<false>(m->xg, io->x, 2.0f / (float)img, img, m->dxbuf, st);
             const float* x_all = io->x;
             int nall = n;
             if (m->a_constrained) {
                 // second encoder pass first: d Rec_z / d z_rec = -2 rho (z - z_rec) / (n zd), through the shared layers down to x_hat
                 const size_t nz = (size_t)n * zd;
                 const float cz = 2.0f * m->cfg.rho / (float)nz;
-                hipLaunchKernelGGL((diff_scale_kernel<false>), dim3(blocks256(nz)), dim3(256), 0, st, m->a_zm + nz, m->a_zm, cz, nz, m->dzr);       // cz (z_rec - z)
+                k_diff_scale<false>(m->a_zm + nz, m->a_zm, cz, nz, m->dzr, st);       // cz (z_rec - z)
                 a_encode_backward(m, m->dzr, io->mask_sigma, n, n, cp_rows, m->Gx, st);
-                hipLaunchKernelGGL(add_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->dxbuf, m->Gx, img);      // + the path through z_rec
+                k_add(m->dxbuf, m->Gx, img, st);      // + the path through z_rec
                 HIP_TRY(hipMemcpyAsync(m->a_xcat, io->x, img * sizeof(float), hipMemcpyDeviceToDevice, st));
                 HIP_TRY(hipMemcpyAsync(m->a_xcat + img, m->xg, img * sizeof(float), hipMemcpyDeviceToDevice, st));
                 x_all = m->a_xcat; nall = 2 * n;
@@ -867,7 +935,7 @@ int aae_phase(uad_gan* m, int phase, const uad_gan_io_t* io, int n, int want_bac
             a_decode_backward(m, m->a_zm, io->mask_g, m->dxbuf, n, m->dzbuf, st);
             if (m->a_constrained) {
                 const size_t nz = (size_t)n * zd;
-                hipLaunchKernelGGL((diff_scale_kernel<true>), dim3(blocks256(nz)), dim3(256), 0, st, m->a_zm, m->a_zm + nz, 2.0f * m->cfg.rho / (float)nz, nz, m->dzbuf);   // + 2 rho (z - z_rec)/(n zd)
+                k_diff_scale<true>(m->a_zm, m->a_zm + nz, 2.0f * m->cfg.rho / (float)nz, nz, m->dzbuf, st);   // + 2 rho (z - z_rec)/(n zd)
             }
             a_encode_backward(m, m->dzbuf, io->mask_z, n, 0, cp_rows, nullptr, st);
             a_encode_wgrads(m, x_all, nall, cp_rows, st);
@@ -885,13 +953,13 @@ int aae_phase(uad_gan* m, int phase, const uad_gan_io_t* io, int n, int want_bac
         reduce_to<0>(m, 0, m->a_crit[0], nullptr, (size_t)n, 1.0f / (float)n, nullptr, st);
         reduce_to<0>(m, 1, m->a_crit[1], nullptr, (size_t)n, 1.0f / (float)n, nullptr, st);
         reduce_to<0>(m, 2, m->a_crit[2], nullptr, (size_t)n, 1.0f, nullptr, st);
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, UAD_GAN_DISCRIMINATOR, m->raw, 0.0f, scal);
+        k_combine(UAD_GAN_DISCRIMINATOR, m->raw, 0.0f, scal, st);
         if (want_backward) uad_launch_reduce_partials(m->a_slab, n, (int)m->a_nd, 1.0f, Gr(m, m->a_w1), st);
     } else {
         // optim_gen (:43,65): -mean d_ over the variables whose name contains 'Encoder'
         a_critic(m, 1, m->a_zm, nullptr, nullptr, n, st);
         reduce_to<0>(m, 0, m->a_crit[0], nullptr, (size_t)n, 1.0f / (float)n, nullptr, st);
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, UAD_GAN_GENERATOR, m->raw, 0.0f, scal);
+        k_combine(UAD_GAN_GENERATOR, m->raw, 0.0f, scal, st);
         if (want_backward) {
             a_encode_backward(m, m->dzbuf, io->mask_z, n, 0, cp_rows, nullptr, st);
             a_encode_wgrads(m, io->x, n, cp_rows, st);
@@ -1075,12 +1143,12 @@ void s_enc_forward(uad_gan* m, const float* x, int n, hipStream_t st) {
     }
     uad_launch_conv_f(dense_desc(n, m->flat, m->cfg.zdim), in, no_xform(), P(m, m->e_dw), m->zr, epi_bias(P(m, m->e_db)), st, nullptr, m->ws);
     const size_t nz = (size_t)n * m->cfg.zdim;
-    hipLaunchKernelGGL(tanh_kernel, dim3(blocks256(nz)), dim3(256), 0, st, m->zr, nz, m->z);
+    k_tanh(m->zr, nz, m->z, st);
 }
 void s_enc_backward(uad_gan* m, const float* x, int n, hipStream_t st) {
     const int zd = m->cfg.zdim;
     const size_t nz = (size_t)n * zd;
-    hipLaunchKernelGGL(tanh_bwd_kernel, dim3(blocks256(nz)), dim3(256), 0, st, m->dzbuf, m->z, (const float*)nullptr, nz, m->dzr);
+    k_tanh_bwd(m->dzbuf, m->z, nullptr, nz, m->dzr, st);
     const UadConvDesc dd = dense_desc(n, m->flat, zd);
     uad_launch_conv_w(dd, m->ea[m->E.size()], no_xform(), m->dzr, no_xform(), Gr(m, m->e_dw), m->wpartial, st);
     uad_launch_colsum(m->dzr, n, zd, Gr(m, m->e_db), m->colscratch, st);
@@ -1107,9 +1175,7 @@ void s_gen_backward(uad_gan* m, const float* z, const float* dx, int n, bool pg,
     RB& L = m->GB.back();
     const int rows = n * L.Hout * L.Hout, HW = L.Hout * L.Hout;
     {
-        const int rpb = (rows + 1023) / 1024, blocks = (rows + rpb - 1) / rpb;
-        hipLaunchKernelGGL(gfinal_bwd_kernel, dim3(blocks), dim3(256), 0, st, dx, m->xg, m->s_hf, P(m, m->g_fw), rows, rpb, L.Cout, linear ? 2 : 1, m->Ga,
-                           pg ? m->finpart : nullptr);
+        const int blocks = k_gfinal_bwd(dx, m->xg, m->s_hf, P(m, m->g_fw), rows, L.Cout, linear ? 2 : 1, m->Ga, pg ? m->finpart : nullptr, kGfinalBlocks, st);
         if (pg) {
             uad_launch_reduce_partials(m->finpart, blocks, L.Cout + 1, 1.0f, m->colscratch, st);
             hipMemcpyAsync(Gr(m, m->g_fw), m->colscratch, L.Cout * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -1237,11 +1303,11 @@ void zim_forward(uad_gan* m, const float* xin, const float* eps, int n, int n_va
         g_conv_d(m, L.d, n, m->ga[i], L.w, P(m, L.b), nullptr, m->gc[i + 1], st);
         z_act_fwd(m->gc[i + 1], (size_t)n * asz(L), m->ga[i + 1], st);
     }
-    hipLaunchKernelGGL(flip_taps_kernel, dim3(1), dim3(256), 0, st, P(m, m->z_fw), 16, 16, m->z_wflip);
+    k_flip_taps(P(m, m->z_fw), 16, 16, m->z_wflip, st);
     UadConvDesc df = m->z_fd; df.N = n;
     uad_launch_conv_first_dgrad_plain(df, m->ga[m->G.size()], m->z_wflip, m->xg, st);
     const size_t img = (size_t)n * H * H;
-    hipLaunchKernelGGL(add_scalar_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->xg, P(m, m->z_fb), img);
+    k_add_scalar(m->xg, P(m, m->z_fb), img, st);
 }
 // dxh = d loss / d x_hat in m->dxbuf; klw = weight of a sample's KL term; pg: also every parameter gradient; anomaly (optional, [n_vae]):
 // |x - x_hat| * |d loss_vae / d x| of the sampled branch (trainers/ceVAE.py:51)
@@ -1252,7 +1318,7 @@ void zim_backward(uad_gan* m, const float* xin, const float* eps, int n, int n_v
     // final conv: kernel gradient in the reversed-tap layout, then un-reversed; bias; data gradient = the "forward" of the image-side relation
     if (pg) {
         uad_launch_conv_first_wgrad(df, m->dxbuf, m->ga[m->G.size()], m->z_dwflip, m->wpartial, st);
-        hipLaunchKernelGGL(flip_taps_kernel, dim3(1), dim3(256), 0, st, m->z_dwflip, 16, 16, Gr(m, m->z_fw));
+        k_flip_taps(m->z_dwflip, 16, 16, Gr(m, m->z_fw), st);
         uad_launch_colsum(m->dxbuf, n * H * H, 1, Gr(m, m->z_fb), m->colscratch, st);
     }
     uad_launch_conv_first_fwd(df, m->dxbuf, m->z_wflip, nullptr, g, st);
@@ -1313,9 +1379,9 @@ int zim_phase(uad_gan* m, const uad_gan_io_t* io, int n, int want_backward, hipS
         reduce_to<2>(m, 0, m->a_xcat, m->xg, img, 1.0f / (float)n, m->z_l1, st);                         // Rec_vae
         reduce_to<2>(m, 1, m->a_xcat + img, m->xg + img, img, 1.0f / (float)n, m->z_l1 + img, st);       // Rec_ce
         reduce_to<0>(m, 2, m->v_kl, nullptr, (size_t)n, 1.0f / (float)n, nullptr, st);                   // kl
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, 6, m->raw, 0.0f, scal);
+        k_combine(6, m->raw, 0.0f, scal, st);
         if (want_backward) {
-            hipLaunchKernelGGL(sign_scale_kernel, dim3(blocks256(2 * img)), dim3(256), 0, st, m->xg, m->a_xcat, 1.0f / (float)n, 2 * img, m->dxbuf);
+            k_sign_scale(m->xg, m->a_xcat, 1.0f / (float)n, 2 * img, m->dxbuf, st);
             zim_backward(m, m->a_xcat, io->eps, 2 * n, n, 1.0f / (float)n, want_backward == 1, io->anomaly, st);
         }
         if (io->reconstruction) HIP_TRY(hipMemcpyAsync(io->reconstruction, m->xg, img * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1328,9 +1394,9 @@ int zim_phase(uad_gan* m, const uad_gan_io_t* io, int n, int want_backward, hipS
     zim_forward(m, io->x, io->eps, n, n, st);
     reduce_to<2>(m, 0, io->x, m->xg, img, 1.0f / (float)n, io->l1_map, st);                       // reconstructionLoss (trainers/VAE.py:36-38)
     reduce_to<0>(m, 1, m->v_kl, nullptr, (size_t)n, 1.0f / (float)n, nullptr, st);                 // kl (:39-41)
-    hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, 3, m->raw, 1.0f, scal);
+    k_combine(3, m->raw, 1.0f, scal, st);
     if (want_backward) {
-        hipLaunchKernelGGL(sign_scale_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->xg, io->x, 1.0f / (float)n, img, m->dxbuf);
+        k_sign_scale(m->xg, io->x, 1.0f / (float)n, img, m->dxbuf, st);
         zim_backward(m, io->x, io->eps, n, n, 1.0f / (float)n, true, nullptr, st);
     }
     if (io->reconstruction) HIP_TRY(hipMemcpyAsync(io->reconstruction, m->xg, img * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1372,8 +1438,7 @@ void you_forward(uad_gan* m, const uad_gan_io_t* io, const float* x, int n, floa
     for (size_t i = 0; i + 1 < m->y_dec.size(); ++i) {
         YOp& o = m->y_dec[i];
         if (o.kind == 2) {
-            const size_t t4 = (size_t)n * o.Hout * o.Hout * cin / 4;
-            hipLaunchKernelGGL(up2_fwd_kernel, dim3(blocks256(t4)), dim3(256), 0, st, in, hin, hin, cin, t4, o.a);
+            up2_fwd(in, n, hin, cin, o.a, st);
         } else {
             UadConvDesc d = o.L.d; d.N = n;
             if (o.kind == 0 && d.CB % 4) uad_launch_conv_first_fwd(d, in, P(m, o.L.w), P(m, o.L.b), o.c, st);
@@ -1385,11 +1450,11 @@ void you_forward(uad_gan* m, const uad_gan_io_t* io, const float* x, int n, floa
     }
     // y_mu
     const YOp& F = m->y_dec.back();
-    hipLaunchKernelGGL(flip_taps_kernel, dim3(3), dim3(256), 0, st, P(m, F.L.w), 9, 64, m->z_wflip);
+    k_flip_taps(P(m, F.L.w), 9, 64, m->z_wflip, st);
     UadConvDesc df = m->y_fd; df.N = n;
     uad_launch_conv_first_dgrad_plain(df, in, m->z_wflip, m->xg, st);
     const size_t img = (size_t)n * H * H;
-    hipLaunchKernelGGL(add_scalar_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->xg, P(m, F.L.b), img);
+    k_add_scalar(m->xg, P(m, F.L.b), img, st);
 }
 // dxh = d objective / d x_hat; leaves d objective / d c of the FIRST encoder conv in *g_first (for the caller's input gradient)
 void you_backward(uad_gan* m, const uad_gan_io_t* io, const float* x, const float* dxh, int n, float inv, bool pg, float** g_first, hipStream_t st) {
@@ -1401,7 +1466,7 @@ void you_backward(uad_gan* m, const uad_gan_io_t* io, const float* x, const floa
     UadConvDesc df = m->y_fd; df.N = n;
     if (pg) {
         uad_launch_conv_first_wgrad(df, dxh, fin, m->z_dwflip, m->wpartial, st);
-        hipLaunchKernelGGL(flip_taps_kernel, dim3(3), dim3(256), 0, st, m->z_dwflip, 9, 64, Gr(m, F.L.w));
+        k_flip_taps(m->z_dwflip, 9, 64, Gr(m, F.L.w), st);
         uad_launch_colsum(dxh, n * H * H, 1, Gr(m, F.L.b), m->colscratch, st);
     }
     uad_launch_conv_first_fwd(df, dxh, m->z_wflip, nullptr, g, st);
@@ -1410,8 +1475,7 @@ void you_backward(uad_gan* m, const uad_gan_io_t* io, const float* x, const floa
         const float* in = i == 0 ? m->a_zm : m->y_dec[i - 1].a;
         const int hin = i == 0 ? r : m->y_dec[i - 1].Hout, cin = i == 0 ? m->gm_Z : m->y_dec[i - 1].Cout;
         if (o.kind == 2) {
-            const size_t t4 = (size_t)n * hin * hin * cin / 4;
-            hipLaunchKernelGGL(up2_bwd_kernel, dim3(blocks256(t4)), dim3(256), 0, st, g, hin, hin, cin, t4, gn);
+            up2_bwd(g, n, hin, cin, gn, st);
             float* t = g; g = gn; gn = t;
             continue;
         }
@@ -1484,14 +1548,14 @@ int you_phase(uad_gan* m, const uad_gan_io_t* io, const float* x, int n, int wan
         float* scal = io->scalars ? io->scalars : m->scalars_own;
         reduce_to<2>(m, 0, x, m->xg, img, 1.0f / (float)n, io->l1_map, st);
         uad_launch_colsum(m->y_loc, L, 3, m->raw + 1, m->colscratch, st);            // sums over locations of con, w-prior, c-prior
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, 7, m->raw, 1.0f / (float)n, scal);
+        k_combine(7, m->raw, 1.0f / (float)n, scal, st);
         if (io->reconstruction) HIP_TRY(hipMemcpyAsync(io->reconstruction, m->xg, img * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (io->z_enc) HIP_TRY(hipMemcpyAsync(io->z_enc, m->a_zm, (size_t)L * m->gm_Z * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     if (!want_backward) return UAD_OK;
     const float* dxh;
     if (restore) { uad_launch_tv_dxhat(x, m->xg, n, H, H, 1.0f, tv, m->gm_dxhat, st); dxh = m->gm_dxhat; }
-    else { hipLaunchKernelGGL(sign_scale_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->xg, x, 1.0f / (float)n, img, m->dxbuf); dxh = m->dxbuf; }
+    else { k_sign_scale(m->xg, x, 1.0f / (float)n, img, m->dxbuf, st); dxh = m->dxbuf; }
     float* g0 = nullptr;
     you_backward(m, io, x, dxh, n, inv, !restore, &g0, st);
     if (restore) {
@@ -1616,11 +1680,10 @@ static int gan_phase_body(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n
         HIP_TRY(hipMemcpyAsync(m->din, m->xg, img * sizeof(float), hipMemcpyDeviceToDevice, st));
         disc_fwd(n, true);
         reduce_to<0>(m, 0, m->Dd, nullptr, (size_t)n * P2, 1.0f / (float)(n * P2), nullptr, st);
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, phase, m->raw, m->cfg.kappa, scal);
+        k_combine(phase, m->raw, m->cfg.kappa, scal, st);
         if (want_backward) {
             Coef4 cf{{-1.0f / (float)(n * P2), 0.f, 0.f, 0.f}};
-            const size_t t4 = (size_t)n * P2 * FC / 4;
-            hipLaunchKernelGGL(topgrad_kernel, dim3(blocks256(t4)), dim3(256), 0, st, P(m, m->d_hw), n * P2, FC, t4, cf, top);
+            k_topgrad(P(m, m->d_hw), n * P2, FC, (size_t)n * P2, cf, top, st);
             disc_bwd(n, false, 0, -1, m->dxbuf);
             gen_bwd(io->z, true, nullptr);
         }
@@ -1629,7 +1692,7 @@ static int gan_phase_body(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n
         // trainers/fAnoGAN.py:50-58,74
         if ((!av && !io->z) || !io->x || !io->alpha) return fail(UAD_ERR_INVALID, "critic phase needs io.x, io.z and io.alpha");
         gen_fwd(io->z);
-        hipLaunchKernelGGL(interp_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->xg, io->x, io->alpha, (int)HW, img, m->din);
+        k_interp(m->xg, io->x, io->alpha, (int)HW, img, m->din, st);
         m->exact_from = 2 * n;                     // the x_hat third of pass A and all of pass B fix the penalty's VALUE: exact fp32 (see g_conv_f)
         disc_fwd(3 * n, true);                                                                    // pass A
         m->exact_from = 0;
@@ -1638,17 +1701,16 @@ static int gan_phase_body(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n
         // pass B: ddx = d sum(d_hat) / d x_hat on samples [2n, 3n)
         {
             Coef4 one{{1.f, 1.f, 1.f, 1.f}};
-            const size_t t4 = (size_t)n * P2 * FC / 4;
             if (rn) {
                 const RB& LB = m->DB.back();
-                hipLaunchKernelGGL(topgrad_kernel, dim3(blocks256(t4)), dim3(256), 0, st, P(m, m->d_hw), n * P2, FC, t4, one, LB.DOUT + (size_t)3 * n * LB.sout);
+                k_topgrad(P(m, m->d_hw), n * P2, FC, (size_t)n * P2, one, LB.DOUT + (size_t)3 * n * LB.sout, st);
                 RbBwd a{n, (size_t)2 * n, (size_t)3 * n, false, 0, true, -1};
                 for (int k = (int)m->DB.size() - 1; k >= 0; --k) rb_backward(m, m->DB[k], a, st);
                 UadConvDesc d0 = m->s_d0; d0.N = n;
                 uad_launch_conv_first_dgrad_plain(d0, m->s_dout0 + (size_t)3 * n * HW * m->dim, P(m, m->s_d0w), m->Gx, st);
             } else {
                 float* u = m->Ga; float* un = m->Gb;
-                hipLaunchKernelGGL(topgrad_kernel, dim3(blocks256(t4)), dim3(256), 0, st, P(m, m->d_hw), n * P2, FC, t4, one, u);
+                k_topgrad(P(m, m->d_hw), n * P2, FC, (size_t)n * P2, one, u, st);
                 for (int i = L - 1; i >= 0; --i) {
                     const Block& B = m->D[i];
                     const size_t per = asz(B);
@@ -1665,13 +1727,12 @@ static int gan_phase_body(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n
         }
         m->exact_from = -1;
         const int cols = n * H;
-        hipLaunchKernelGGL(pen_col_kernel, dim3(blocks256(cols)), dim3(256), 0, st, m->Gx, n, H, H, m->slopes, m->redpart);
-        uad_launch_reduce_partials(m->redpart, (int)blocks256(cols), 1, m->cfg.scale / (float)cols, m->raw + 2, st);
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, phase, m->raw, m->cfg.kappa, scal);
+        const int pen_blocks = k_pen_col(m->Gx, n, H, H, m->slopes, m->redpart, st);
+        uad_launch_reduce_partials(m->redpart, pen_blocks, 1, m->cfg.scale / (float)cols, m->raw + 2, st);
+        k_combine(phase, m->raw, m->cfg.kappa, scal, st);
         if (want_backward) {
             // pass C, bottom-up: adjoint of pass B.  ubar_0 = d penalty / d ddx lives in din's tail.
-            hipLaunchKernelGGL(pen_grad_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->Gx, m->slopes,
-                               m->cfg.scale * 2.0f / (float)cols, H, H, img, m->din + 3 * img);
+            k_pen_grad(m->Gx, m->slopes, m->cfg.scale * 2.0f / (float)cols, H, H, img, m->din + 3 * img, st);
             if (rn) {
                 UadConvDesc d0 = m->s_d0; d0.N = n;
                 uad_launch_conv_first_fwd(d0, m->din + 3 * img, P(m, m->s_d0w), nullptr, m->s_out0 + (size_t)3 * n * HW * m->dim, st);
@@ -1693,11 +1754,9 @@ static int gan_phase_body(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n
             // pass D: ordinary backward of all 3n samples; top gradient +1/(n P) fake, -1/(n P) real, 0 for x_hat
             const float k = 1.0f / (float)(n * P2);
             Coef4 cf{{k, -k, 0.f, 1.f}};
-            const size_t t4 = (size_t)3 * n * P2 * FC / 4;
-            hipLaunchKernelGGL(topgrad_kernel, dim3(blocks256(t4)), dim3(256), 0, st, P(m, m->d_hw), n * P2, FC, t4, cf, top);
+            k_topgrad(P(m, m->d_hw), n * P2, FC, (size_t)3 * n * P2, cf, top, st);
             {   // Dense(1): kernel gradient over the 3n feature rows (coefficient per third) + pass C's adjoint rows (coefficient 1)
-                const int rows = 4 * n * P2, rpb = (rows + 255) / 256, blocks = (rows + rpb - 1) / rpb;
-                hipLaunchKernelGGL(coef_colsum_kernel, dim3(blocks), dim3(256), 0, st, feat, rows, rpb, n * P2, FC, cf, m->finpart);
+                const int blocks = k_coef_colsum(feat, 4 * n * P2, n * P2, FC, cf, m->finpart, kCoefColsumBlocks, st);
                 uad_launch_reduce_partials(m->finpart, blocks, FC, 1.0f, Gr(m, m->d_hw), st);
                 gan_grad_final(m, m->d_hw);
                 // Dense(1) bias: +1/(nP) over the fake rows, -1/(nP) over the real rows = 0 (stays at its zero initialisation)
@@ -1710,9 +1769,9 @@ static int gan_phase_body(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n
         gen_fwd(nullptr);
         reduce_to<2>(m, 0, io->x, m->xg, img, 1.0f / (float)n, io->l1_map, st);
         reduce_to<0>(m, 1, m->v_kl, nullptr, (size_t)n, 1.0f / (float)n, nullptr, st);
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, 3, m->raw, m->cfg.kl_weight, scal);
+        k_combine(3, m->raw, m->cfg.kl_weight, scal, st);
         if (want_backward) {
-            hipLaunchKernelGGL(sign_scale_kernel, dim3(blocks256(img)), dim3(256), 0, st, m->xg, io->x, 1.0f / (float)n, img, m->dxbuf);
+            k_sign_scale(m->xg, io->x, 1.0f / (float)n, img, m->dxbuf, st);
             gen_bwd(nullptr, true, m->dzbuf);
             v_enc_backward(m, io, n, m->cfg.kl_weight / (float)n, st);
         }
@@ -1732,12 +1791,11 @@ static int gan_phase_body(uad_gan_t* m, int phase, const uad_gan_io_t* io, int n
         reduce_to<1>(m, 0, io->x, m->xg, img, 1.0f / (float)img, nullptr, st);
         reduce_to<1>(m, 1, f_enc, f_real, nf, 1.0f / (float)nf, nullptr, st);
         reduce_to<2>(m, 2, io->x, m->xg, img, 1.0f / (float)n, io->l1_map, st);
-        hipLaunchKernelGGL(combine_kernel, dim3(1), dim3(64), 0, st, phase, m->raw, m->cfg.kappa, scal);
+        k_combine(phase, m->raw, m->cfg.kappa, scal, st);
         if (want_backward) {
-            hipLaunchKernelGGL((diff_scale_kernel<false>), dim3(blocks256(nf)), dim3(256), 0, st, f_enc, f_real,
-                               m->cfg.kappa * 2.0f / (float)nf, nf, top);
+            k_diff_scale<false>(f_enc, f_real, m->cfg.kappa * 2.0f / (float)nf, nf, top, st);
             disc_bwd(n, false, 0, -1, m->dxbuf);
-            hipLaunchKernelGGL((diff_scale_kernel<true>), dim3(blocks256(img)), dim3(256), 0, st, m->xg, io->x, 2.0f / (float)img, img, m->dxbuf);
+            k_diff_scale<true>(m->xg, io->x, 2.0f / (float)img, img, m->dxbuf, st);
             gen_bwd(m->z, false, m->dzbuf);
             if (rn) s_enc_backward(m, io->x, n, st); else enc_backward(m, io->x, io->mask_z, n, st);
         }
@@ -1763,7 +1821,7 @@ static int gan_reconstruct_body(uad_gan_t* m, const uad_gan_io_t* io, int n, voi
     else { enc_forward(m, io->x, io->mask_z, n, st); gen_forward(m, m->z, io->mask_g, n, st); }
     if (io->reconstruction) HIP_TRY(hipMemcpyAsync(io->reconstruction, m->xg, img * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (io->z_enc) HIP_TRY(hipMemcpyAsync(io->z_enc, m->variant == UAD_GAN_AAE ? m->a_zm : m->z, (size_t)n * m->cfg.zdim * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (io->l1_map) hipLaunchKernelGGL((sum_kernel<2>), dim3(256), dim3(256), 0, st, io->x, m->xg, img, io->l1_map, m->redpart);
+    if (io->l1_map) k_sum<2>(io->x, m->xg, img, io->l1_map, m->redpart, st);
     HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
@@ -1835,5 +1893,7 @@ int uad_gan_adam(uad_gan_t* m, int group, float lr, float beta1, float beta2, fl
     HIP_TRY(hipGetLastError());
     return UAD_OK;
 }
+
+#include "uad_gan_ops.inc"
 
 }  // extern "C"
